@@ -21,6 +21,13 @@ Rank 0 prints ONE JSON line (contract in the task statement) with two extra obje
                 measured with HIP events on the launch stream in a second, instrumented replay of the
                 same K steps (so the events do not perturb `value`); peak 8.0 TB/s HBM.
   cpu_baseline  the scalar C/torch oracle port (oracle/) timed on this host, rank 0, N=1 only.
+
+A plain run (no --full) sets up, settles, warms up, times the K steps through both paths (three streams, batch
+entry point) and prints the line.  What needs runs of its own is null there: cpu_baseline, regions, gpu_state,
+single_stream_value, warm_index_value, three_frame_step, batch_period_events, timed_configuration_check; `roofline`
+holds only the timed region's fraction, `multi_gpu` only the collective check.  --full runs all of it after the
+timed region, as every run did before the option existed.  --dump-outputs DIR writes the rows the headline path
+returned in its last timed step (dump_outputs).
 """
 import argparse
 import json
@@ -110,6 +117,32 @@ ROUNDS = max(1, int(os.environ.get("LINK_BENCH_ROUNDS", "8")))   # a step = ROUN
 SETTLE_STEPS = int(os.environ.get("LINK_BENCH_SETTLE", "60"))      # untimed steps before the warm-up (clock ramp); reported in the line.
 # (500 until the step became a batch of 24 frames: three regions of the timed shape are 50 ms at the driver's --steps 20, and the
 # figure is the same with 60 as with 500 -- 34.7 / 35.0 against 35.3 / 35.7 us/frame, alternating on one box)
+SETTLE_REGION_MAX = 200     # steps per settling region at most: with a large K the settling stays ~0.5 s instead of growing with K
+
+
+def settle_shape(steps):
+    """(regions, steps per region) of the untimed settling phase before the warm-up: regions of the timed shape (K steps between
+    synchronisations), at least 3 and at least SETTLE_STEPS steps in all, a region capped at SETTLE_REGION_MAX steps (a timed
+    region that long is no short burst; below the cap the shape is K steps, as it always was)."""
+    k = max(1, min(steps, SETTLE_REGION_MAX))
+    return max(3, -(-SETTLE_STEPS // k)), k
+
+
+DUMP_BYTES = 64 * 1000 * 1000    # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(dirname, rows):
+    """--dump-outputs: frame j's result rows -- what the timed path returned for it in its last step -- as float32 DIR/frame<j>.npy.
+    When the frames hold more than DUMP_BYTES in all (cfg2: 3 x 100k x 64 x 4 B = 76.8 MB), every frame keeps the same fixed sample of
+    rows: seed 0, row indices sorted, the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n, c = rows[0].shape
+    keep = min(n, DUMP_BYTES // (4 * c * len(rows)))
+    idx = None if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    for j, r in enumerate(rows):
+        a = r.float().cpu().numpy()
+        np.save(os.path.join(dirname, f"frame{j}.npy"), a if idx is None else a[idx])
 
 
 def s_uniform(n, grid=256, seed=0):
@@ -822,7 +855,14 @@ def main():
     ap.add_argument("--voxels", type=int, default=100_000)
     ap.add_argument("--channels", type=int, default=64)
     ap.add_argument("--streams", type=int, default=3, help="independent frames in flight per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2: also run the side measurements and checks of the line (one frame in flight, warm index, three-frame step, "
+                         "batch period events, clock / power state, timed-geometry check, instrumented per-kernel roofline, CPU baseline, "
+                         "module-surface regions, N > 1 gather figures); without it the run times the headline and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cfg2: after the timed steps, write the rows the timed path returned in its last step, one float32 "
+                         "DIR/frame<j>.npy per frame in flight (a fixed, seeded row sample when all frames exceed 64 MB)")
     ap.add_argument("--bev", action="store_true",
                     help="cfg5: also run the dense BEV half (RPN + CenterHead in plain torch, harness/bevhead.py) behind the backbone")
     ap.add_argument("--io", choices=("f32", "f16", "bf16"), default="f32",
@@ -833,6 +873,8 @@ def main():
                          "frames sharded over the ranks (strong scaling), encoder eval forward, maps built per frame; cfg5 = labelled: "
                          "sparse half of the detection backbone (SpMiddleResNetFHDELKv3) on one S-nusc frame per rank")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload != "cfg2":
+        raise SystemExit("bench.py: --dump-outputs is implemented for the headline workload (cfg2) only")
 
     import torch
     import torch.distributed as dist
@@ -1017,20 +1059,24 @@ def main():
     # long run.  tools/graphstep.py, 20-step regions back to back on one box: 39.3 38.8 38.3 37.2 36.7 36.1 ... settling at 34.8-35.0
     # us/frame after ~10 regions (a 600-step run on the same box: 33.2): a device that has just worked through one long burst
     # answers the first short bursts 10 % slower, so a 2 ms timed region has to be preceded by bursts of its own length.  Same
-    # step count as before (>= SETTLE_STEPS; a fixed number of regions: every rank passes the same barriers).
+    # step count as before (>= SETTLE_STEPS; a fixed number of regions: every rank passes the same barriers).  Regions are capped at
+    # SETTLE_REGION_MAX steps (settle_shape), so that the untimed time of a run does not grow with K.
     import gc
-    for _ in range(max(3, -(-SETTLE_STEPS // max(args.steps, 1)))):
-        timed(args.steps)
+    settle_regions, settle_k = settle_shape(args.steps)
+    for _ in range(settle_regions):
+        timed(settle_k)
     gc.collect()
     gc.disable()                                     # no collection inside the warm-up / timed regions (re-enabled right after)
     timed(max(args.warmup, 1))
     elapsed = timed(args.steps)                      # THE measurement (cold: index rebuilt for every frame)
-    elapsed_r1 = timed(args.steps, rounds=1)         # the same K steps with the 3-frame batch of rounds 1-4 (continuity)
+    outs_timed = [o.clone() for o in last_out]       # the rows the timed steps wrote, in the row type they were written in
+    elapsed_r1 = timed(args.steps, rounds=1) if args.full else None   # the same K steps with the 3-frame batch of rounds 1-4 (continuity)
     # ---- the same K steps through the BATCH entry point (include/link_amd.h section H): the frames of a step go through calls of FB
     # frames (two steps' worth; a last call takes what is left), two arena sets, submit(s + 1) before join(s) from one stream.  Same
     # contract: settling regions of the timed shape, W warm-up steps, EXACTLY K steps between barrier + synchronize.  The faster of the
     # two ways to run the K steps is the line's `value` (both are in the line: `paths`); rows are bit-equal (checked below).
-    elapsed_batch, batch_fail = None, None
+    elapsed_batch, batch_fail, outs_batch = None, None, None
+    batch_last = [None]                              # the rows the last call of the latest timed_batch returned
 
     def timed_batch(k):
         frames_total, done, s_, prev_ = k * NS * ROUNDS, 0, 0, None
@@ -1040,7 +1086,7 @@ def main():
         t0 = time.perf_counter()
         while done < frames_total:
             nb = min(FB, frames_total - done)
-            _, tk_ = bsets[s_ % 2].submit(bfe0[:nb], bco0[:nb], stream=h_)
+            batch_last[0], tk_ = bsets[s_ % 2].submit(bfe0[:nb], bco0[:nb], stream=h_)
             if prev_ is not None:
                 bsets[0].join(prev_, stream=h_)
             prev_, done, s_ = tk_, done + nb, s_ + 1
@@ -1058,9 +1104,11 @@ def main():
     if batch_usable:
         try:
             for _ in range(3):
-                timed_batch(args.steps)
+                timed_batch(settle_k)
             timed_batch(max(args.warmup, 1))
             elapsed_batch = timed_batch(args.steps)
+            if args.dump_outputs is not None:        # frames 0 .. NS - 1 of the last call (call item i runs frame i % NS)
+                outs_batch = [o.clone() for o in batch_last[0][:NS]]
             bsets[0].check()
         except Exception as e:  # noqa: BLE001
             if world > 1:
@@ -1068,9 +1116,8 @@ def main():
             batch_fail, elapsed_batch = repr(e)[:200], None
     gc.enable()
     # what was just timed is what gets checked: every plan's output under the timed configuration (NS frames in flight,
-    # their launch geometry), kept for the comparison with the single-frame geometry below and with the oracle
+    # their launch geometry), kept (outs_timed, above) for the comparison with the single-frame geometry below and with the oracle
     batch_probe("after the timed region")
-    outs_timed = [o.clone() for o in last_out]       # the rows the timed steps wrote, in the row type they were written in
     for pl in plans:
         pl.check()
     # device-event view of the same configuration (SURVEY.md 8d asks for event medians): one event per stream after every
@@ -1091,26 +1138,28 @@ def main():
         return {"median_us": round(per[len(per) // 2], 2), "mean_us": round(sum(per) / len(per), 2), "n": len(per),
                 "note": "HIP events, one per stream after every frame: interval between consecutive completions on one stream = "
                         "time of one batch of the frames in flight, steady state"}
-    batch_ev = batch_period_events(max(50, min(args.steps, 200)))
-    # clock / power state of the device under this very load (a replay of >= 30 ms of the timed steps; rank 0 reports it)
-    if rank == 0:
-        gpu_state = gpu_state_during(lambda: timed(max(args.steps, 1000), rounds=1), local_rank)
-    else:
-        gpu_state = None
-        timed(max(args.steps, 1000), rounds=1)       # every rank passes the same barriers
-    elapsed_single = timed(args.steps * NS, ns=1)    # the same number of frames, one in flight
     M = plan.blocks()
-    timed_check = {"frames": NS, "bitwise_equal_to_single_frame_geometry": True, "max_rel_err_vs_single_frame_geometry": 0.0}
-    for j in range(NS):
-        o1 = plans[j].run(frames[j][0], frames[j][1])          # same frame, single-frame launch geometry
+    checksum = float(outs_timed[0].double().sum().item())   # frame 0's rows as the timed steps wrote them
+    batch_ev = gpu_state = elapsed_single = timed_check = elapsed_warm = out = None
+    if args.full:                                   # the side measurements of the line: runs of their own after the timed region
+        batch_ev = batch_period_events(max(50, min(args.steps, 200)))
+        # clock / power state of the device under this very load (a replay of >= 30 ms of the timed steps; rank 0 reports it)
+        if rank == 0:
+            gpu_state = gpu_state_during(lambda: timed(max(args.steps, 1000), rounds=1), local_rank)
+        else:
+            gpu_state = None
+            timed(max(args.steps, 1000), rounds=1)       # every rank passes the same barriers
+        elapsed_single = timed(args.steps * NS, ns=1)    # the same number of frames, one in flight
+        timed_check = {"frames": NS, "bitwise_equal_to_single_frame_geometry": True, "max_rel_err_vs_single_frame_geometry": 0.0}
+        for j in range(NS):
+            o1 = plans[j].run(frames[j][0], frames[j][1])          # same frame, single-frame launch geometry
+            torch.cuda.synchronize()
+            d = float((outs_timed[j].float() - o1.float()).abs().max() / o1.float().abs().max())
+            timed_check["max_rel_err_vs_single_frame_geometry"] = max(timed_check["max_rel_err_vs_single_frame_geometry"], d)
+            timed_check["bitwise_equal_to_single_frame_geometry"] &= bool(torch.equal(outs_timed[j], o1))
+        out = plan.run(feats, coords)
         torch.cuda.synchronize()
-        d = float((outs_timed[j].float() - o1.float()).abs().max() / o1.float().abs().max())
-        timed_check["max_rel_err_vs_single_frame_geometry"] = max(timed_check["max_rel_err_vs_single_frame_geometry"], d)
-        timed_check["bitwise_equal_to_single_frame_geometry"] &= bool(torch.equal(outs_timed[j], o1))
-    out = plan.run(feats, coords)
-    torch.cuda.synchronize()
-    checksum = float(out.double().sum().item())
-    elapsed_warm = timed(args.steps, build_index=False)
+        elapsed_warm = timed(args.steps, build_index=False)
 
     # ---- max over ranks + the trivial result gather (per-frame summaries only; link_amd/parallel.py)
     multi = None
@@ -1126,53 +1175,58 @@ def main():
         if float(ones.item()) != float(world):           # fail loudly: a job whose collective does not span --gpus ranks measured something else
             raise SystemExit(f"bench.py: all_reduce of ones gave {float(ones.item())} on rank {rank}, expected {world} "
                              f"(backend {dist.get_backend()}): the process group does not span --gpus {args.gpus} ranks")
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps * ROUNDS):
-            for j in range(NS):
-                with torch.cuda.stream(streams[j]):
-                    last_out[j] = plans[j].run(frames[j][0], frames[j][1])
-        torch.cuda.synchronize()
-        probe = torch.tensor([[float(rank), float(N), float(M), checksum]], dtype=torch.float64, device=cdev)
-        gather_frame_rows(probe)
-        if backend == "nccl":
-            torch.cuda.synchronize()
-        t_e2e = time.perf_counter() - t0
-        payload = out.float() if backend == "nccl" else out.float().cpu()
-        gather_frame_rows(payload[:16])                   # warm the collective up
-        t_full = []
-        for _ in range(3):
+        multi = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "all_reduce_of_ones": float(ones.item()),
+                 "collective_spans_all_ranks": bool(float(ones.item()) == float(world))}
+        if args.full:
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            full = gather_frame_rows(payload)
+            for _ in range(args.steps * ROUNDS):
+                for j in range(NS):
+                    with torch.cuda.stream(streams[j]):
+                        last_out[j] = plans[j].run(frames[j][0], frames[j][1])
+            torch.cuda.synchronize()
+            probe = torch.tensor([[float(rank), float(N), float(M), checksum]], dtype=torch.float64, device=cdev)
+            gather_frame_rows(probe)
             if backend == "nccl":
                 torch.cuda.synchronize()
-            t_full.append(time.perf_counter() - t0)
-        full_ok = bool(full.shape[0] == world * N and torch.equal(full[rank * N:(rank + 1) * N].to(payload.device), payload))
-        side = torch.tensor([t_e2e, min(t_full), 1.0 if full_ok else 0.0], dtype=torch.float64, device=cdev)
-        dist.all_reduce(side[:2], op=dist.ReduceOp.MAX)
-        dist.all_reduce(side[2:], op=dist.ReduceOp.MIN)
-        multi = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "all_reduce_of_ones": float(ones.item()),
-                 "collective_spans_all_ranks": bool(float(ones.item()) == float(world)),
-                 "end_to_end_ms": round(1e3 * float(side[0]), 4),
-                 "end_to_end_note": f"{args.steps} timed steps + the per-frame summary gather, one host clock around both, max over ranks",
-                 "full_tensor_gather_ms": round(1e3 * float(side[1]), 4),
-                 "full_tensor_gather_bytes_per_rank": int(N * C * 4),
-                 "full_tensor_gather_ok": bool(float(side[2]) == 1.0),
-                 "full_tensor_gather_note": "all_gather of every rank's fp32 [N, C] result rows (sizes, then padded payload), best of 3, max "
-                                            "over ranks; reported separately, never inside `value` (SURVEY.md 8e)"}
-        mine = torch.tensor([[float(rank), float(N), float(M), checksum, elapsed, elapsed_warm, elapsed_single, elapsed_r1,
+            t_e2e = time.perf_counter() - t0
+            payload = out.float() if backend == "nccl" else out.float().cpu()
+            gather_frame_rows(payload[:16])                   # warm the collective up
+            t_full = []
+            for _ in range(3):
+                barrier()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                full = gather_frame_rows(payload)
+                if backend == "nccl":
+                    torch.cuda.synchronize()
+                t_full.append(time.perf_counter() - t0)
+            full_ok = bool(full.shape[0] == world * N and torch.equal(full[rank * N:(rank + 1) * N].to(payload.device), payload))
+            side = torch.tensor([t_e2e, min(t_full), 1.0 if full_ok else 0.0], dtype=torch.float64, device=cdev)
+            dist.all_reduce(side[:2], op=dist.ReduceOp.MAX)
+            dist.all_reduce(side[2:], op=dist.ReduceOp.MIN)
+            multi.update({"end_to_end_ms": round(1e3 * float(side[0]), 4),
+                          "end_to_end_note": f"{args.steps} timed steps + the per-frame summary gather, one host clock around both, max over ranks",
+                          "full_tensor_gather_ms": round(1e3 * float(side[1]), 4),
+                          "full_tensor_gather_bytes_per_rank": int(N * C * 4),
+                          "full_tensor_gather_ok": bool(float(side[2]) == 1.0),
+                          "full_tensor_gather_note": "all_gather of every rank's fp32 [N, C] result rows (sizes, then padded payload), best of 3, max "
+                                                     "over ranks; reported separately, never inside `value` (SURVEY.md 8e)"})
+
+        def neg(x):                                      # a figure this run did not measure (no --full) travels as -1
+            return -1.0 if x is None else float(x)
+        mine = torch.tensor([[float(rank), float(N), float(M), checksum, elapsed, neg(elapsed_warm), neg(elapsed_single), neg(elapsed_r1),
                               1.0 if affinity["pinned"] else 0.0, float(-1 if affinity["numa_node"] is None else affinity["numa_node"]),
                               float(affinity["cpus"]), float(-1 if affinity["first_cpu"] is None else affinity["first_cpu"]),
-                              float(-1.0 if elapsed_batch is None else elapsed_batch)]],
+                              neg(elapsed_batch)]],
                             dtype=torch.float64, device=cdev)
         rows = gather_frame_rows(mine).cpu()
         elapsed = float(rows[:, 4].max())
-        elapsed_warm = float(rows[:, 5].max())
-        elapsed_single = float(rows[:, 6].max())
-        elapsed_r1 = float(rows[:, 7].max())
+        if args.full:
+            elapsed_warm = float(rows[:, 5].max())
+            elapsed_single = float(rows[:, 6].max())
+            elapsed_r1 = float(rows[:, 7].max())
         elapsed_batch = float(rows[:, 12].max()) if bool((rows[:, 12] > 0).all()) else None
         total_vox = float(rows[:, 1].sum())
         rank_rows = [{"rank": int(r[0]), "voxels": int(r[1]), "blocks": int(r[2]), "checksum": float(r[3])}
@@ -1189,200 +1243,201 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- instrumented replay: per-kernel durations with HIP events on the launch stream ---------
-    import ctypes
-    lib = L.lib()
-    geometry(1)
-    st = torch.cuda.current_stream().cuda_stream
-    b, desc = plan.buf, plan.desc
     esz = 4 if args.io == "f32" else 2
     ab = alg_bytes(N, M, C, esz=esz)
-    if plan.dense:
-        g = plan.dcg
-        # the three launches of one step (index -> pre_mix+modulate+cell sums -> box sum+de-modulate); C = 64
-        stages = {
-            "index": (lambda: lib.link_dc_index_ids(coords.data_ptr(), N, ctypes.byref(g), b.cnt, b.sid, b.vcell, b.hdr, st))
-            if b.tune.k1_form == 1 else
-            (lambda: lib.link_dc_index(coords.data_ptr(), N, ctypes.byref(g), b.cnt, b.slots, b.vcell, b.hdr, st)),
-            "premix_modsum": lambda: lib.link_dc_premix_modsum(ctypes.byref(b), ctypes.byref(g), ctypes.byref(desc), N, 0, st),
-            "gather_demod": lambda: lib.link_dc_gather_demod(ctypes.byref(b), ctypes.byref(g), ctypes.byref(desc), N, st),
-        }
-        table = ab["block_gather"]
-        kab = {"index": N * 16, "premix_modsum": N * esz * C + table, "gather_demod": table + N * esz * C}
-        if C != 64:                                   # other widths: box sum and de-modulation are two kernels
-            del stages["gather_demod"], kab["gather_demod"]
-            stages["gather"] = lambda: lib.link_dc_gather(b.S, b.cell_n, ctypes.byref(desc), ctypes.byref(g), b.A, st)
-            stages["demod"] = lambda: lib.link_dc_demod(b.A, b.fin, coords.data_ptr(), b.vcell, b.w_pos, b.alpha, b.ln_w,
-                                                        b.ln_b, ctypes.byref(desc), ctypes.byref(g), N, b.out, 0, st)
-            kab.update({"gather": table, "demod": N * esz * C})
-    elif getattr(plan, "tiles", False):
-        grid = plan.grid                               # general layout, tile form: index + two launches
-        stages = {
-            "index_build(4 kernels)": lambda: lib.link_index_build(
-                coords.data_ptr(), N, ctypes.byref(grid), b.cell_counts, b.scratch, b.scratch_bytes, b.cell_blk,
-                b.vox_blk, b.idx_query, b.perm, b.vox_sorted, b.pos_blk, b.blk_start, b.blk_coords, b.counts, b.hdr, st),
-            "premix_modsum_tiles": lambda: lib.link_elk_premix_modsum_tiles(
-                b.feats, b.vox_sorted, b.pos_blk, b.blk_start, b.hdr, b.w_pre, b.pre_ln_w, b.pre_ln_b, b.w_pos, b.alpha,
-                ctypes.byref(desc), N, N, b.S, b.s_bytes, b.fin, st),
-            "gather_demod_tiles": lambda: lib.link_elk_gather_demod_tiles(
-                b.S, b.fin, b.vox_sorted, b.pos_blk, b.blk_coords, b.cell_blk, ctypes.byref(grid), b.hdr, b.w_pos, b.alpha,
-                b.ln_w, b.ln_b, ctypes.byref(desc), N, N, b.out, st),
-        }
-        table = ab["block_gather"]
-        kab = {"premix_modsum_tiles": N * 16 + N * esz * C + table, "gather_demod_tiles": table + N * esz * C}
-    else:
-        grid = plan.grid
-        stages = {
-            "index_build(4 kernels)": lambda: lib.link_index_build(
-                coords.data_ptr(), N, ctypes.byref(grid), b.cell_counts, b.scratch, b.scratch_bytes, b.cell_blk,
-                b.vox_blk, b.idx_query, b.perm, b.vox_sorted, b.pos_blk, b.blk_start, b.blk_coords, b.counts, b.hdr, st),
-            "premix_ln": lambda: lib.link_premix_ln(b.feats, b.w_pre, b.pre_ln_w, b.pre_ln_b, N, C, 1e-6, b.fin, st),
-            "modulate_block_sum": lambda: lib.link_modulate_block_sum(
-                b.fin, b.vox_sorted, b.w_pos, b.alpha, b.blk_start, b.hdr, ctypes.byref(desc), N, N, b.S, st),
-            "block_gather": lambda: lib.link_block_gather(
-                b.S, b.blk_coords, b.cell_blk, ctypes.byref(grid), b.hdr, ctypes.byref(desc), N, b.A, st),
-            "voxel_demod_ln": lambda: lib.link_voxel_demod_ln(
-                b.A, b.fin, b.vox_sorted, b.pos_blk, b.w_pos, b.alpha, b.ln_w, b.ln_b, b.hdr, ctypes.byref(desc),
-                N, b.out, st),
-        }
-        kab = {k: ab[k] for k in ("premix_ln", "modulate_block_sum", "block_gather", "voxel_demod_ln")}
-    assert abs(sum(kab.values()) - ab["total"]) <= 16 * N, "per-kernel split must add up to B_alg"
-    k_inst = min(args.steps, 100)
-    evs = {name: [] for name in stages}
-    for _ in range(k_inst):
-        for name, fn in stages.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            evs[name].append((e0, e1))
-    torch.cuda.synchronize()
-    kern_us = {name: 1e3 * sum(x.elapsed_time(y) for x, y in v) / len(v) for name, v in evs.items()}
-    # whole single-frame steps, device-event timed one by one: median and mean
-    step_ev = []
-    for _ in range(max(50, min(args.steps, 200))):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        plan.run(feats, coords)
-        e1.record()
-        step_ev.append((e0, e1))
-    torch.cuda.synchronize()
-    step_us = sorted(1e3 * x.elapsed_time(y) for x, y in step_ev)
-    core = {k: v for k, v in kern_us.items() if k in kab}
-    dom1 = max(core, key=core.get)
-    # ---- the same three stages in the TIMED geometry (NS frames in flight on NS streams), device events around every launch: what a
-    # kernel costs while the other frames' kernels run beside it.  (An instrumented replay: the timed region itself is never touched.)
-    live = None
-    if plan.dense and C == 64 and NS > 1:
-        geometry(NS)
-        sh = [s_.cuda_stream for s_ in streams]
-        bj = [plans[j].buf for j in range(NS)]
-        for j in range(NS):
-            bj[j].feats, bj[j].coords = frames[j][0].data_ptr(), frames[j][1].data_ptr()
-        tev = {k: [] for k in ("index", "premix_modsum", "gather_demod")}
-        for it in range(min(args.steps, 60) + 5):
-            for j in range(NS):
-                with torch.cuda.stream(streams[j]):
-                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-                    ev[0].record()
-                    lib.link_dc_index(bj[j].coords, N, ctypes.byref(g), bj[j].cnt, bj[j].slots, bj[j].vcell, bj[j].hdr, sh[j])
-                    ev[1].record()
-                    lib.link_dc_premix_modsum(ctypes.byref(bj[j]), ctypes.byref(g), ctypes.byref(desc), N, 0, sh[j])
-                    ev[2].record()
-                    lib.link_dc_gather_demod(ctypes.byref(bj[j]), ctypes.byref(g), ctypes.byref(desc), N, sh[j])
-                    ev[3].record()
-                if it >= 5:
-                    for q, k in enumerate(tev):
-                        tev[k].append((ev[q], ev[q + 1]))
-        torch.cuda.synchronize()
-        live = {k: round(1e3 * sum(a.elapsed_time(b_) for a, b_ in v) / len(v), 2) for k, v in tev.items()}
-        geometry(1)
-    # ---- per-kernel figures of the TIMED geometry from the committed rocprofv3 files (profiles/timed_geometry.json, built by
-    # tools/r06_profiles.sh + tools/timed_geometry_json.py from the kernel trace of THIS command and the PMC passes over the same
-    # geometry): frac = algorithmic bytes per launch / (csv average us) / 8 TB/s -- reproducible from profiles/ by hand
-    tg, tg_kern, traffic_frame = None, {}, None
-    tgp = os.path.join(ROOT, "profiles", "timed_geometry.json")
-    if os.path.exists(tgp) and (N, C) == (100000, 64) and args.io == "f32" and plan.dense:
-        tg = json.load(open(tgp))
-        for k, v in tg.get("kernels", {}).items():
-            if k in kab:
-                tg_kern[k] = {"rocprof_name": v["rocprof_name"], "avg_us": v["avg_us"], "launches": v["launches"], "alg_bytes_per_launch": kab[k],
-                              "achieved_gbs": round(kab[k] / (v["avg_us"] * 1e-6) / 1e9, 1),
-                              "frac": round(kab[k] / (v["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                              "traffic_bytes_per_launch": v.get("traffic_bytes_per_launch"),
-                              "live_event_us_this_run": (live or {}).get(k)}
-        if tg_kern and all(v.get("traffic_bytes_per_launch") for v in tg_kern.values()):
-            traffic_frame = int(sum(v["traffic_bytes_per_launch"] for v in tg_kern.values()))
-    clock_hz, clock_src = SHADER_CLOCK_HZ, "nominal 2.4 GHz (no amdsmi reading)"
-    if gpu_state and gpu_state.get("sclk_mhz"):
-        clock_hz, clock_src = gpu_state["sclk_mhz"]["median"] * 1e6, "amdsmi median shader clock during a replay of the timed steps"
     us_frame = 1e6 * elapsed / (args.steps * NS * ROUNDS)
-    dom = max(tg_kern, key=lambda k: tg_kern[k]["avg_us"]) if tg_kern else dom1
-    mfma_cyc = (tg or {}).get("kernels", {}).get("premix_modsum", {}).get("mfma_busy_cycles_per_launch")
-    mfma_us = tg_kern.get("premix_modsum", {}).get("avg_us")
     # The headline of the object is the TIMED REGION: B_alg of a frame over the region's time per frame.  The step is three kernels of
     # similar length that overlap across the frames in flight, so no single launch "is" the step; `kernel` names the longest launch of
     # the timed geometry and `timed_geometry.kernels` carries every launch's own figures (rocprofv3 averages of the committed CSV).
-    roofline = {"bound": "hbm", "kernel": (tg_kern[dom]["rocprof_name"] if tg_kern else dom), "achieved": round(ab["total"] / (us_frame * 1e-6) / 1e9, 1),
+    roofline = {"bound": "hbm", "achieved": round(ab["total"] / (us_frame * 1e-6) / 1e9, 1),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ab["total"] / (us_frame * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                 "what": "timed region: B_alg of one frame (SURVEY.md 8d) / measured time per frame / 8 TB/s -- the same number as whole_step.frac",
-                "alg_bytes_per_frame": ab["total"], "traffic": traffic_frame,
-                "traffic_what": ("memory-side bytes per FRAME in the timed geometry (sum over the three launches; rocprofv3 --pmc, 2*FETCH_SIZE + WRITE_SIZE)"
-                                 if traffic_frame else None),
-                "timed_geometry": ({"source_kernel_stats": tg["source_kernel_stats"], "source_pmc": tg["source_pmc"], "commit": tg["commit"],
-                                    "geometry": tg["geometry"], "dominant": dom, "kernels": tg_kern,
-                                    "sum_of_launches_over_frames_in_flight_us": round(sum(v["avg_us"] for v in tg_kern.values()) / NS, 2),
-                                    "frac_if_the_launches_tiled_without_gaps": round(ab["total"] / (sum(v["avg_us"] for v in tg_kern.values()) / NS * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "note": "frac = alg_bytes_per_launch / (avg_us of the committed CSV) / 8 TB/s; live_event_us_this_run = the same "
-                                            "launch bracketed by HIP events on its stream in an instrumented replay of the timed geometry (the bracket holds the stream-ordered "
-                                            "launch boundary too: 3-6 us more than the kernel's own duration in the trace).  The launches "
-                                            "of the frames in flight share the chip (about three are running at any moment), so a launch's OWN fraction "
-                                            "is about a third of what the chip sustains meanwhile: the region's fraction is `roofline.frac`, and the sum "
-                                            "of the three launch durations over the frames in flight is its lower bound for these kernels"}
-                                   if tg_kern else None),
-                "layout": "dense-cell" if plan.dense else "general",
-                # north_star: MFMA utilisation of the kernel that holds the dense contraction = SQ_VALU_MFMA_BUSY_CYCLES (cycles, summed over the
-                # chip's 1024 SIMDs; PMC pass in the timed geometry) / (its rocprofv3 duration x 1024 SIMDs x clock)
-                "mfma_util": ({"kernel": "premix_modsum", "busy_cycles_per_launch": mfma_cyc,
-                               "frac": round(mfma_cyc / (mfma_us * 1e-6 * 1024 * clock_hz), 4), "clock_hz": clock_hz, "clock_source": clock_src,
-                               "note": "SQ_VALU_MFMA_BUSY_CYCLES / (kernel us x 1024 SIMDs x shader clock); the contraction is 0.82 GFLOP per frame -- "
-                                       "not a grading bound (SURVEY.md 8d)"} if mfma_cyc and mfma_us else None),
+                "alg_bytes_per_frame": ab["total"], "layout": "dense-cell" if plan.dense else "general",
                 "whole_step": {"alg_bytes": ab["total"], "us": round(us_frame, 2),
                                "frac": round(ab["total"] / (us_frame * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                               "note": "per frame: B_alg of one frame over the timed region's time per frame"},
-                "single_frame_geometry": {"what": "ONE frame in flight (other launch geometry: matrix-core sums pre_mix at 1024 workgroups): per-stage HIP events "
-                                                  "around the stage calls, and whole steps one by one -- NOT the timed region",
-                                          "kernel_us_events": {k: round(v, 2) for k, v in kern_us.items()},
-                                          "dominant": dom1, "dominant_frac": round(kab[dom1] / (core[dom1] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                          "step_median_us": round(step_us[len(step_us) // 2], 2), "step_mean_us": round(sum(step_us) / len(step_us), 2),
-                                          "n": len(step_us),
-                                          "frac": round(ab["total"] / (step_us[len(step_us) // 2] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}}
+                               "note": "per frame: B_alg of one frame over the timed region's time per frame"}}
+    tg = kab = cpu = regions = None
+    if args.full:
+        # ---- instrumented replay: per-kernel durations with HIP events on the launch stream ---------
+        import ctypes
+        lib = L.lib()
+        geometry(1)
+        st = torch.cuda.current_stream().cuda_stream
+        b, desc = plan.buf, plan.desc
+        if plan.dense:
+            g = plan.dcg
+            # the three launches of one step (index -> pre_mix+modulate+cell sums -> box sum+de-modulate); C = 64
+            stages = {
+                "index": (lambda: lib.link_dc_index_ids(coords.data_ptr(), N, ctypes.byref(g), b.cnt, b.sid, b.vcell, b.hdr, st))
+                if b.tune.k1_form == 1 else
+                (lambda: lib.link_dc_index(coords.data_ptr(), N, ctypes.byref(g), b.cnt, b.slots, b.vcell, b.hdr, st)),
+                "premix_modsum": lambda: lib.link_dc_premix_modsum(ctypes.byref(b), ctypes.byref(g), ctypes.byref(desc), N, 0, st),
+                "gather_demod": lambda: lib.link_dc_gather_demod(ctypes.byref(b), ctypes.byref(g), ctypes.byref(desc), N, st),
+            }
+            table = ab["block_gather"]
+            kab = {"index": N * 16, "premix_modsum": N * esz * C + table, "gather_demod": table + N * esz * C}
+            if C != 64:                                   # other widths: box sum and de-modulation are two kernels
+                del stages["gather_demod"], kab["gather_demod"]
+                stages["gather"] = lambda: lib.link_dc_gather(b.S, b.cell_n, ctypes.byref(desc), ctypes.byref(g), b.A, st)
+                stages["demod"] = lambda: lib.link_dc_demod(b.A, b.fin, coords.data_ptr(), b.vcell, b.w_pos, b.alpha, b.ln_w,
+                                                            b.ln_b, ctypes.byref(desc), ctypes.byref(g), N, b.out, 0, st)
+                kab.update({"gather": table, "demod": N * esz * C})
+        elif getattr(plan, "tiles", False):
+            grid = plan.grid                               # general layout, tile form: index + two launches
+            stages = {
+                "index_build(4 kernels)": lambda: lib.link_index_build(
+                    coords.data_ptr(), N, ctypes.byref(grid), b.cell_counts, b.scratch, b.scratch_bytes, b.cell_blk,
+                    b.vox_blk, b.idx_query, b.perm, b.vox_sorted, b.pos_blk, b.blk_start, b.blk_coords, b.counts, b.hdr, st),
+                "premix_modsum_tiles": lambda: lib.link_elk_premix_modsum_tiles(
+                    b.feats, b.vox_sorted, b.pos_blk, b.blk_start, b.hdr, b.w_pre, b.pre_ln_w, b.pre_ln_b, b.w_pos, b.alpha,
+                    ctypes.byref(desc), N, N, b.S, b.s_bytes, b.fin, st),
+                "gather_demod_tiles": lambda: lib.link_elk_gather_demod_tiles(
+                    b.S, b.fin, b.vox_sorted, b.pos_blk, b.blk_coords, b.cell_blk, ctypes.byref(grid), b.hdr, b.w_pos, b.alpha,
+                    b.ln_w, b.ln_b, ctypes.byref(desc), N, N, b.out, st),
+            }
+            table = ab["block_gather"]
+            kab = {"premix_modsum_tiles": N * 16 + N * esz * C + table, "gather_demod_tiles": table + N * esz * C}
+        else:
+            grid = plan.grid
+            stages = {
+                "index_build(4 kernels)": lambda: lib.link_index_build(
+                    coords.data_ptr(), N, ctypes.byref(grid), b.cell_counts, b.scratch, b.scratch_bytes, b.cell_blk,
+                    b.vox_blk, b.idx_query, b.perm, b.vox_sorted, b.pos_blk, b.blk_start, b.blk_coords, b.counts, b.hdr, st),
+                "premix_ln": lambda: lib.link_premix_ln(b.feats, b.w_pre, b.pre_ln_w, b.pre_ln_b, N, C, 1e-6, b.fin, st),
+                "modulate_block_sum": lambda: lib.link_modulate_block_sum(
+                    b.fin, b.vox_sorted, b.w_pos, b.alpha, b.blk_start, b.hdr, ctypes.byref(desc), N, N, b.S, st),
+                "block_gather": lambda: lib.link_block_gather(
+                    b.S, b.blk_coords, b.cell_blk, ctypes.byref(grid), b.hdr, ctypes.byref(desc), N, b.A, st),
+                "voxel_demod_ln": lambda: lib.link_voxel_demod_ln(
+                    b.A, b.fin, b.vox_sorted, b.pos_blk, b.w_pos, b.alpha, b.ln_w, b.ln_b, b.hdr, ctypes.byref(desc),
+                    N, b.out, st),
+            }
+            kab = {k: ab[k] for k in ("premix_ln", "modulate_block_sum", "block_gather", "voxel_demod_ln")}
+        assert abs(sum(kab.values()) - ab["total"]) <= 16 * N, "per-kernel split must add up to B_alg"
+        k_inst = min(args.steps, 100)
+        evs = {name: [] for name in stages}
+        for _ in range(k_inst):
+            for name, fn in stages.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                evs[name].append((e0, e1))
+        torch.cuda.synchronize()
+        kern_us = {name: 1e3 * sum(x.elapsed_time(y) for x, y in v) / len(v) for name, v in evs.items()}
+        # whole single-frame steps, device-event timed one by one: median and mean
+        step_ev = []
+        for _ in range(max(50, min(args.steps, 200))):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            plan.run(feats, coords)
+            e1.record()
+            step_ev.append((e0, e1))
+        torch.cuda.synchronize()
+        step_us = sorted(1e3 * x.elapsed_time(y) for x, y in step_ev)
+        core = {k: v for k, v in kern_us.items() if k in kab}
+        dom1 = max(core, key=core.get)
+        # ---- the same three stages in the TIMED geometry (NS frames in flight on NS streams), device events around every launch: what a
+        # kernel costs while the other frames' kernels run beside it.  (An instrumented replay: the timed region itself is never touched.)
+        live = None
+        if plan.dense and C == 64 and NS > 1:
+            geometry(NS)
+            sh = [s_.cuda_stream for s_ in streams]
+            bj = [plans[j].buf for j in range(NS)]
+            for j in range(NS):
+                bj[j].feats, bj[j].coords = frames[j][0].data_ptr(), frames[j][1].data_ptr()
+            tev = {k: [] for k in ("index", "premix_modsum", "gather_demod")}
+            for it in range(min(args.steps, 60) + 5):
+                for j in range(NS):
+                    with torch.cuda.stream(streams[j]):
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                        ev[0].record()
+                        lib.link_dc_index(bj[j].coords, N, ctypes.byref(g), bj[j].cnt, bj[j].slots, bj[j].vcell, bj[j].hdr, sh[j])
+                        ev[1].record()
+                        lib.link_dc_premix_modsum(ctypes.byref(bj[j]), ctypes.byref(g), ctypes.byref(desc), N, 0, sh[j])
+                        ev[2].record()
+                        lib.link_dc_gather_demod(ctypes.byref(bj[j]), ctypes.byref(g), ctypes.byref(desc), N, sh[j])
+                        ev[3].record()
+                    if it >= 5:
+                        for q, k in enumerate(tev):
+                            tev[k].append((ev[q], ev[q + 1]))
+            torch.cuda.synchronize()
+            live = {k: round(1e3 * sum(a.elapsed_time(b_) for a, b_ in v) / len(v), 2) for k, v in tev.items()}
+            geometry(1)
+        # ---- per-kernel figures of the TIMED geometry from the committed rocprofv3 files (profiles/timed_geometry.json, built by
+        # tools/r06_profiles.sh + tools/timed_geometry_json.py from the kernel trace of THIS command and the PMC passes over the same
+        # geometry): frac = algorithmic bytes per launch / (csv average us) / 8 TB/s -- reproducible from profiles/ by hand
+        tg, tg_kern, traffic_frame = None, {}, None
+        tgp = os.path.join(ROOT, "profiles", "timed_geometry.json")
+        if os.path.exists(tgp) and (N, C) == (100000, 64) and args.io == "f32" and plan.dense:
+            tg = json.load(open(tgp))
+            for k, v in tg.get("kernels", {}).items():
+                if k in kab:
+                    tg_kern[k] = {"rocprof_name": v["rocprof_name"], "avg_us": v["avg_us"], "launches": v["launches"], "alg_bytes_per_launch": kab[k],
+                                  "achieved_gbs": round(kab[k] / (v["avg_us"] * 1e-6) / 1e9, 1),
+                                  "frac": round(kab[k] / (v["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                  "traffic_bytes_per_launch": v.get("traffic_bytes_per_launch"),
+                                  "live_event_us_this_run": (live or {}).get(k)}
+            if tg_kern and all(v.get("traffic_bytes_per_launch") for v in tg_kern.values()):
+                traffic_frame = int(sum(v["traffic_bytes_per_launch"] for v in tg_kern.values()))
+        clock_hz, clock_src = SHADER_CLOCK_HZ, "nominal 2.4 GHz (no amdsmi reading)"
+        if gpu_state and gpu_state.get("sclk_mhz"):
+            clock_hz, clock_src = gpu_state["sclk_mhz"]["median"] * 1e6, "amdsmi median shader clock during a replay of the timed steps"
+        dom = max(tg_kern, key=lambda k: tg_kern[k]["avg_us"]) if tg_kern else dom1
+        mfma_cyc = (tg or {}).get("kernels", {}).get("premix_modsum", {}).get("mfma_busy_cycles_per_launch")
+        mfma_us = tg_kern.get("premix_modsum", {}).get("avg_us")
+        roofline.update({"kernel": (tg_kern[dom]["rocprof_name"] if tg_kern else dom), "traffic": traffic_frame,
+                         "traffic_what": ("memory-side bytes per FRAME in the timed geometry (sum over the three launches; rocprofv3 --pmc, 2*FETCH_SIZE + WRITE_SIZE)"
+                                          if traffic_frame else None),
+                         "timed_geometry": ({"source_kernel_stats": tg["source_kernel_stats"], "source_pmc": tg["source_pmc"], "commit": tg["commit"],
+                                             "geometry": tg["geometry"], "dominant": dom, "kernels": tg_kern,
+                                             "sum_of_launches_over_frames_in_flight_us": round(sum(v["avg_us"] for v in tg_kern.values()) / NS, 2),
+                                             "frac_if_the_launches_tiled_without_gaps": round(ab["total"] / (sum(v["avg_us"] for v in tg_kern.values()) / NS * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                             "note": "frac = alg_bytes_per_launch / (avg_us of the committed CSV) / 8 TB/s; live_event_us_this_run = the same "
+                                                     "launch bracketed by HIP events on its stream in an instrumented replay of the timed geometry (the bracket holds the stream-ordered "
+                                                     "launch boundary too: 3-6 us more than the kernel's own duration in the trace).  The launches "
+                                                     "of the frames in flight share the chip (about three are running at any moment), so a launch's OWN fraction "
+                                                     "is about a third of what the chip sustains meanwhile: the region's fraction is `roofline.frac`, and the sum "
+                                                     "of the three launch durations over the frames in flight is its lower bound for these kernels"}
+                                            if tg_kern else None),
+                         # north_star: MFMA utilisation of the kernel that holds the dense contraction = SQ_VALU_MFMA_BUSY_CYCLES (cycles, summed over the
+                         # chip's 1024 SIMDs; PMC pass in the timed geometry) / (its rocprofv3 duration x 1024 SIMDs x clock)
+                         "mfma_util": ({"kernel": "premix_modsum", "busy_cycles_per_launch": mfma_cyc,
+                                        "frac": round(mfma_cyc / (mfma_us * 1e-6 * 1024 * clock_hz), 4), "clock_hz": clock_hz, "clock_source": clock_src,
+                                        "note": "SQ_VALU_MFMA_BUSY_CYCLES / (kernel us x 1024 SIMDs x shader clock); the contraction is 0.82 GFLOP per frame -- "
+                                                "not a grading bound (SURVEY.md 8d)"} if mfma_cyc and mfma_us else None),
+                         "single_frame_geometry": {"what": "ONE frame in flight (other launch geometry: matrix-core sums pre_mix at 1024 workgroups): per-stage HIP events "
+                                                           "around the stage calls, and whole steps one by one -- NOT the timed region",
+                                                   "kernel_us_events": {k: round(v, 2) for k, v in kern_us.items()},
+                                                   "dominant": dom1, "dominant_frac": round(kab[dom1] / (core[dom1] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                                   "step_median_us": round(step_us[len(step_us) // 2], 2), "step_mean_us": round(sum(step_us) / len(step_us), 2),
+                                                   "n": len(step_us),
+                                                   "frac": round(ab["total"] / (step_us[len(step_us) // 2] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}})
 
-    # ---- CPU baseline: the oracle on this host (rank 0, N=1 only) -------------------------------------
-    # (1) the OpenMP twin of the C restatement -- pragmas exactly where the reference's CPU ops have them
-    #     (voxelize_cpu.cpp:17 inner loop, devoxelize_cpu.cpp:16 outer loop), OMP_NUM_THREADS = physical
-    #     cores -- on a bounded sample of the same frame; (2) the same code scalar, one core, full frame.
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(blk, feats.float(), coords, outs_timed[0].float(), N, C, S_, R, G)   # the TIMED configuration's output
+        # ---- CPU baseline: the oracle on this host (rank 0, N=1 only) -------------------------------------
+        # (1) the OpenMP twin of the C restatement -- pragmas exactly where the reference's CPU ops have them
+        #     (voxelize_cpu.cpp:17 inner loop, devoxelize_cpu.cpp:16 outer loop), OMP_NUM_THREADS = physical
+        #     cores -- on a bounded sample of the same frame; (2) the same code scalar, one core, full frame.
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(blk, feats.float(), coords, outs_timed[0].float(), N, C, S_, R, G)   # the TIMED configuration's output
 
-    batch_probe("before the module-surface regions")
-    regions = timed_regions(la, blk, feats.float(), coords, C, S_, R) if (world == 1 and args.io == "f32") else None
-    batch_probe("after the module-surface regions")
+        batch_probe("before the module-surface regions")
+        regions = timed_regions(la, blk, feats.float(), coords, C, S_, R) if (world == 1 and args.io == "f32") else None
+        batch_probe("after the module-surface regions")
     ms = 1e3 * elapsed / args.steps
     frames_timed = args.steps * NS * ROUNDS          # per GPU
     line = {
         "metric": "voxels/s through one LinK (3x7)^3 block, 100k active voxels C=64",
         "value": round(total_vox * frames_timed / elapsed, 1), "unit": "voxels/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "settle_steps_before_warmup": max(3, -(-SETTLE_STEPS // max(args.steps, 1))) * args.steps, "ms_per_step": round(ms, 5),
-        "ms_per_step_event_median": round(batch_ev["median_us"] * ROUNDS * 1e-3, 5), "batch_period_events": batch_ev,
+        "steps": args.steps, "warmup": args.warmup, "settle_steps_before_warmup": settle_regions * settle_k, "ms_per_step": round(ms, 5),
+        "ms_per_step_event_median": round(batch_ev["median_us"] * ROUNDS * 1e-3, 5) if batch_ev else None, "batch_period_events": batch_ev,
         "frames_per_step": NS * ROUNDS * world,
         "step_definition_version": 2,   # 1 (rounds 1-4): a step = one batch of the 3 frames in flight; 2 (round 5 on): 8 such batches = 24 frames
                                         # per GPU.  `three_frame_step` is the version-1 figure of the same run
         "three_frame_step": {"us_per_frame": round(1e6 * elapsed_r1 / (args.steps * NS), 2), "ms_per_step": round(1e3 * elapsed_r1 / args.steps, 5),
                              "frac": round(97520688 / (elapsed_r1 / (args.steps * NS)) / 1e9 / HBM_PEAK_GBS, 4) if (N, C) == (100_000, 64) else None,
                              "note": f"the same {args.steps} steps with a batch of {NS} frames per step (what rounds 1-4 timed): a region pays ~150 us "
-                                     "for filling / draining the pipeline around its two synchronisations"},
+                                     "for filling / draining the pipeline around its two synchronisations"} if elapsed_r1 is not None else None,
         "us_per_frame": round(1e6 * elapsed / frames_timed, 2), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if args.io == "f32" else f"{args.io} rows at the boundary, f32 contraction / block table / statistics",
@@ -1398,8 +1453,8 @@ def main():
                            f"{ROUNDS} rounds); value = voxels of all timed frames / time",
                    "parallelism": f"{world} GPU(s) x {NS} independent frames in flight (one HIP stream each), "
                                   "no data-path collective"},
-        "single_stream_value": round(total_vox * frames_timed / elapsed_single, 1),
-        "warm_index_value": round(total_vox * frames_timed / elapsed_warm, 1),
+        "single_stream_value": round(total_vox * frames_timed / elapsed_single, 1) if elapsed_single is not None else None,
+        "warm_index_value": round(total_vox * frames_timed / elapsed_warm, 1) if elapsed_warm is not None else None,
         "timed_configuration_check": timed_check,
         "gpu_state": gpu_state,        # shader / memory clock and socket power under this load (amdsmi)
         "ranks": rank_rows,          # the trivial result gather: one summary row per rank (frame 0 of each rank)
@@ -1429,17 +1484,19 @@ def main():
                 b_.check()
                 ok &= all(torch.equal(outs_b[i], outs_timed[i % NS]) for i in range(FB))
             # the three kernels of a launch set bracketed by timed events on their own streams, in steady state (the last of four calls)
-            bsets[0].set_timing(True)
-            prev_ = None
-            for s_ in range(4):
-                _, tk_ = bsets[s_ % 2].submit(bfe0, bco0, stream=bstream.cuda_stream)
-                if prev_ is not None:
-                    bsets[0].join(prev_, stream=bstream.cuda_stream)
-                prev_ = tk_
-            bsets[0].join(prev_, stream=bstream.cuda_stream)
-            torch.cuda.synchronize()
-            live_b = bsets[0].kernel_times_us(prev_)
-            bsets[0].set_timing(False)
+            live_b = None
+            if args.full:
+                bsets[0].set_timing(True)
+                prev_ = None
+                for s_ in range(4):
+                    _, tk_ = bsets[s_ % 2].submit(bfe0, bco0, stream=bstream.cuda_stream)
+                    if prev_ is not None:
+                        bsets[0].join(prev_, stream=bstream.cuda_stream)
+                    prev_ = tk_
+                bsets[0].join(prev_, stream=bstream.cuda_stream)
+                torch.cuda.synchronize()
+                live_b = bsets[0].kernel_times_us(prev_)
+                bsets[0].set_timing(False)
             usb = 1e6 * elapsed_batch / frames_timed
             fracb = round(ab["total"] / (usb * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
             tgb, bk = (tg or {}).get("batch"), {}
@@ -1459,7 +1516,8 @@ def main():
                                   "batch + persistent pre_mix and gather role kernels fed by per-XCD cursors, per-frame arrival counters instead of "
                                   "launch boundaries), two arena sets, call s + 1 submitted before call s is joined (DESIGN.md 4i)",
                           "frames_per_call": FB, "placement_trials_us_per_frame": btrials, "bitwise_equal_to_the_streams_rows": bool(ok),
-                          "kernel_brackets_us_this_run": {"insert": round(live_b[0], 1), "premix_modsum": round(live_b[1], 1), "gather_demod": round(live_b[2], 1)}}
+                          "kernel_brackets_us_this_run": ({"insert": round(live_b[0], 1), "premix_modsum": round(live_b[1], 1),
+                                                           "gather_demod": round(live_b[2], 1)} if live_b else None)}
             line["paths"]["batch"] = batch_path
             line["batch_entry_point"] = {**batch_path, "calls_in_flight": "submit(s + 1) before join(s), one caller stream", "arena_sets_in_flight": 2,
                                          "bitwise_equal_to_timed_configuration": bool(ok)}
@@ -1490,6 +1548,8 @@ def main():
         except Exception as e:                          # a second path must never cost the line
             line["batch_entry_point"] = {"error": repr(e)[:200]}
     del bsets
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, outs_batch if line["paths"]["headline"] == "batch" else outs_timed)
     print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

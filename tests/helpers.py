@@ -75,3 +75,35 @@ def lidar_like(n_target=60000, seed=0, voxel=0.05, stride=1):
     out = np.zeros((pc.shape[0], 4), np.int32)
     out[:, :3] = pc
     return out
+
+
+def ref_ops_cases():
+    """The seeded inputs of the check of the oracle against the reference's compiled CPU ops (tests/test_oracle_golden.py):
+    op name -> (the reference op's arguments as numpy arrays / ints, a callable returning the oracle's answer).  Shared with
+    tests/golden/make_golden_ref_ops.py, which records the digests of the reference ops' outputs on these inputs."""
+    from oracle import link_oracle as O
+    rng = np.random.default_rng(0)
+    coords = rng.integers(-500, 500, (5000, 4)).astype(np.int32)
+    coords[:, 3] = 0
+    off = O.get_kernel_offsets(3)
+    idx = rng.integers(-1, 300, 5000).astype(np.int32)
+    idxp = np.abs(idx)
+    counts = O.spcount(idxp, 300)
+    feats = rng.standard_normal((5000, 24)).astype(np.float32)
+    top = rng.standard_normal((300, 24)).astype(np.float32)
+    ind = rng.integers(-1, 300, (700, 8)).astype(np.int32)
+    w = rng.random((700, 8)).astype(np.float32)
+    return {"hash_cpu": ((coords,), lambda: O.sphash(coords)),
+            "kernel_hash_cpu": ((coords, off), lambda: O.sphash_offsets(coords, off)),
+            "count_cpu": ((idx, 300), lambda: O.spcount(idx, 300)),
+            "voxelize_forward_cpu": ((feats, idxp, counts), lambda: O.spvoxelize_fwd(feats, idxp, counts)),
+            "voxelize_backward_cpu": ((top, idxp, counts, 5000), lambda: O.spvoxelize_bwd(top, idxp, counts, 5000)),
+            "devoxelize_forward_cpu": ((top, ind, w), lambda: O.spdevoxelize_fwd(top, ind, w))}
+
+
+def array_digest(a):
+    """sha256 of an op output's values (integers as int64, floats as float32: value equality, as np.array_equal checks it)."""
+    import hashlib
+    a = np.asarray(a)
+    a = a.astype(np.int64 if np.issubdtype(a.dtype, np.integer) else np.float32)
+    return {"shape": list(a.shape), "dtype": str(a.dtype), "sha256": hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()}

@@ -1,5 +1,6 @@
-"""bench.py end to end on the GPU box: the default line's contract, and the N > 1 path with two ranks sharing the one
-device over gloo (LINK_BENCH_BACKEND=gloo: the branch exists for exactly this; the real multi-GPU run uses RCCL)."""
+"""bench.py end to end on the GPU box: the plain line's contract and its output dump, the `--full` line, and the N > 1 path with
+two ranks sharing the one device over gloo (LINK_BENCH_BACKEND=gloo: the branch exists for exactly this; the real multi-GPU run uses
+RCCL)."""
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def test_bench_two_ranks_over_gloo_on_one_device():
     """`python bench.py --gpus 2` without a launcher re-executes itself under torch.distributed.run (127.0.0.1 rendezvous),
     every rank times its own frames, rank 0 prints ONE line with n_gpus = 2 and one gathered summary row per rank; the
     rows equal what each rank's frame gives on its own (rank r runs frames with seed r * 64 + k)."""
-    d = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    d = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"],
              {"LINK_BENCH_BACKEND": "gloo", "MASTER_ADDR": "127.0.0.1"})
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak"
     assert [r["rank"] for r in d["ranks"]] == [0, 1]
@@ -42,7 +43,7 @@ def test_bench_two_ranks_over_gloo_on_one_device():
     assert mg["backend"] == "gloo" and mg["world_size"] == 2 and mg["all_reduce_of_ones"] == 2.0 and mg["collective_spans_all_ranks"]
     assert mg["end_to_end_ms"] >= d["ms_per_step"] * d["steps"] * 0.5 and mg["end_to_end_ms"] > 0
     assert mg["full_tensor_gather_ms"] > 0 and mg["full_tensor_gather_ok"] and mg["full_tensor_gather_bytes_per_rank"] == 100000 * 64 * 4
-    single = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"])
+    single = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"])
     assert single["multi_gpu"] is None
     assert "gpu_state" in single and isinstance(single["gpu_state"], dict)          # clock / power state (amdsmi) or why it is missing
     assert single["n_gpus"] == 1 and single["ranks"][0]["blocks"] == d["ranks"][0]["blocks"]
@@ -78,12 +79,45 @@ def test_bench_two_ranks_over_gloo_on_one_device():
     assert "error" not in be and be["us_per_frame"] > 0 and be["bitwise_equal_to_timed_configuration"] and be["frames_per_call"] == 48 and len(be["placement_trials_us_per_frame"]) >= 1
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_the_timed_rows(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the contract fields, exactly K timed steps, none of the side
+    measurements; `--dump-outputs DIR` writes the rows of the timed path's last step (float32, a seeded row sample of each of the
+    three frames, at most 64 MB in all), and two runs with other step counts write the same rows (the inputs are fixed)."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(a)])
+    assert d["metric"] and d["unit"] == "voxels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["us_per_frame"] * d["frames_per_step"] - d["ms_per_step"] * 1e3) < 0.4
+    assert abs(d["value"] - 100000 / (d["us_per_frame"] * 1e-6)) < 1e-3 * d["value"]
+    for k in ("cpu_baseline", "regions", "gpu_state", "single_stream_value", "warm_index_value", "three_frame_step",
+              "batch_period_events", "timed_configuration_check", "multi_gpu"):
+        assert d[k] is None, k
+    assert "single_frame_geometry" not in d["roofline"] and 0 < d["roofline"]["frac"] < 1
+    paths = d["paths"]
+    assert paths["headline"] in ("streams", "batch") and abs(paths[paths["headline"]]["us_per_frame"] - d["us_per_frame"]) < 1e-9
+    if paths["batch"] is not None:
+        assert paths["batch"]["bitwise_equal_to_the_streams_rows"]
+    d2 = _run(["--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", str(b)])
+    assert d2["steps"] == 5
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["frame0.npy", "frame1.npy", "frame2.npy"] and sorted(p.name for p in b.iterdir()) == names
+    total = 0
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype == np.float32 and x.shape == (83333, 64) and np.isfinite(x).all() and float(np.abs(x).max()) > 0
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 * 1000 * 1000
+    assert not np.array_equal(np.load(a / "frame0.npy"), np.load(a / "frame1.npy"))       # three different frames
+
+
 def test_bench_half_rows_check_reads_what_the_step_wrote():
     """`--io f16`: the timed steps write fp16 rows into the plan's per-dtype buffer; the line's checks must be computed from
     THAT buffer (round 3 compared the stale fp32 buffer with itself).  Half tolerances: the single-frame geometry gives the
     same rows up to the fp16 rounding of the output (2^-10 relative to the row's scale), the oracle on the rounded inputs
     agrees to 6e-3 (max-norm)."""
-    d = _run(["--io", "f16", "--steps", "3", "--warmup", "2"], timeout=600)
+    d = _run(["--io", "f16", "--steps", "3", "--warmup", "2", "--full"], timeout=600)
     chk = d["timed_configuration_check"]
     assert chk["frames"] == 3 and 0.0 <= chk["max_rel_err_vs_single_frame_geometry"] < 2e-3
     err = d["cpu_baseline"]["gpu_vs_oracle_max_rel_err"]

@@ -14,7 +14,7 @@ for v in orig ${VARIANTS:-}; do
   echo "== variant $v (pass $rep)" | tee -a $OUT
   [ $rep = 1 ] && timeout 120 python -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $OUT
   for st in 3 1; do
-    timeout 200 python $R/bench.py --steps 300 --warmup 20 --streams $st --no-cpu-baseline 2>/dev/null | python -c "
+    timeout 200 python $R/bench.py --full --steps 300 --warmup 20 --streams $st --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,16 +8,16 @@ OUT=$R/gpurun_out/r05_${TAG:-x}
 rm -rf $OUT; mkdir -p $OUT
 for ST in 3 1; do
   D=$OUT/trace_s$ST; mkdir -p $D
-  timeout 200 rocprofv3 --kernel-trace --stats -d $D -o trace -- python $R/bench.py --steps 100 --warmup 10 --streams $ST --no-cpu-baseline > $D/bench.log 2>&1
+  timeout 200 rocprofv3 --kernel-trace --stats -d $D -o trace -- python $R/bench.py --full --steps 100 --warmup 10 --streams $ST --no-cpu-baseline > $D/bench.log 2>&1
   grep '^{' $D/bench.log > $OUT/bench_under_rocprof_streams$ST.json
   db=$(find $D -name "*.db" | head -1)
   [ -n "$db" ] && python $R/tools/rocpd_stats.py $db $OUT/kernel_stats_streams$ST.csv | head -6
   rm -rf $D
 done
-python $R/bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+python $R/bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 tail -c 400 $OUT/bench_default.json
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_driver_args.json
-timeout 200 python $R/bench.py --io f16 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_f16.json
+python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_driver_args.json
+timeout 200 python $R/bench.py --full --io f16 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_f16.json
 timeout 300 python $R/bench.py --workload cfg3 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg3.json
 timeout 300 python $R/bench.py --workload cfg5 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg5.json
 timeout 300 python $R/bench.py --workload cfg5 --io f16 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg5_f16.json

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/r06_${TAG:-x}
 rm -rf $OUT; mkdir -p $OUT
 for ST in 3 1; do
   D=$OUT/trace_s$ST; mkdir -p $D
-  timeout 300 rocprofv3 --kernel-trace --stats -d $D -o trace -- python $R/bench.py --steps 100 --warmup 10 --streams $ST --no-cpu-baseline > $D/bench.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $D -o trace -- python $R/bench.py --full --steps 100 --warmup 10 --streams $ST --no-cpu-baseline > $D/bench.log 2>&1
   grep '^{' $D/bench.log > $OUT/bench_under_rocprof_streams$ST.json
   db=$(find $D -name "*.db" | head -1)
   [ -n "$db" ] && python $R/tools/rocpd_stats.py $db $OUT/kernel_stats_streams$ST.csv | head -6
@@ -30,14 +30,14 @@ for NS in 3; do
 done
 python $R/tools/timed_geometry_json.py $OUT/kernel_stats_streams3.csv $OUT/pmc_counters_streams3.txt $OUT/timed_geometry.json "${COMMIT:-unknown}" "profiles/r06_${TAG:-x}"
 cp $OUT/timed_geometry.json $R/profiles/timed_geometry.json      # the line below is built from THIS run's profile
-python $R/bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+python $R/bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 tail -c 600 $OUT/bench_default.json
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_driver_args.json
+python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_driver_args.json
 if [ -z "$QUICK" ]; then
 timeout 300 python $R/bench.py --workload cfg3 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg3.json
 timeout 300 python $R/bench.py --workload cfg5 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg5.json
 timeout 300 python $R/bench.py --workload cfg5 --io f16 --steps 30 --warmup 3 2>/dev/null | grep '^{' > $OUT/bench_cfg5_f16.json
-timeout 200 python $R/bench.py --io f16 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_f16.json
+timeout 200 python $R/bench.py --full --io f16 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_f16.json
 # row N1: kernel trace of the cfg3 line (the convolution kernels' averages next to the line's conv_roofline) and of the training step
 D=$OUT/trace_cfg3; mkdir -p $D
 timeout 300 rocprofv3 --kernel-trace --stats -d $D -o trace -- python $R/bench.py --workload cfg3 --steps 30 --warmup 3 > /dev/null 2>&1
