@@ -321,8 +321,10 @@ static int batch_launch(const dc_bt_host_t &c, const dc_bt_frames_t &fr, const d
   if (zsplit > g.dim[2]) zsplit = g.dim[2];
   const int64_t nwg = (int64_t)txn * tyn * g.dim[3] * zsplit;
   if (nwg > (1 << 20)) return LINK_ERR_ARG;
+  // insert items per frame: one per 256 voxels of the largest frame, NOT capped -- an item covers exactly its own 256 voxels, so a
+  // cap dropped every voxel of a larger frame past cap x 256 (the cap of 2048 lost the voxels past 524 288 without a status bit).
+  // The submit's guard n < 2^24 keeps wpf <= 65 536 and the insert's cursor (nframes x wpf <= 48 x 65 536) in int.
   int wpf = (int)((nmax + 255) / 256);
-  if (wpf > 2048) wpf = 2048;
   if (wpf < 1) wpf = 1;
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_batch_k1<OP, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, k1_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_batch_k2<OP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, k2_lds);

@@ -522,7 +522,7 @@ class ElkCoreBatch:
     `frames` arenas (ElkCorePlan buffers, dense-cell layout) are allocated once; `run(feats_list, coords_list)` takes up to that many
     frames and returns their result rows (views of the arenas' `out` buffers, complete in stream order).  Results are bit for bit
     those of `ElkCorePlan.run` per frame.  C = 64, cg = 32, cos / sin, r in {2, 3}, fp32 / fp16 / bf16 rows (one type per call), coord_div = 1, no alpha, slot capacity
-    <= 352 -- LinkAmdError otherwise (run such frames through ElkCorePlan).  Two batches in flight: two ElkCoreBatch objects sharing
+    <= 352, frames of fewer than 2^24 voxels -- LinkAmdError otherwise (run such frames through ElkCorePlan).  Two batches in flight: two ElkCoreBatch objects sharing
     ONE context (`ElkCoreBatch(..., share=first)`), alternated with two streams -- the pre_mix role of the second batch starts
     under the gather role of the first.  `check()` raises if a voxel was dropped or a kernel's bounded wait gave up."""
 
