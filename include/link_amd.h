@@ -483,6 +483,25 @@ int link_ln_add_relu_forward(const float *x, const float *addend, const float *l
                              int64_t n, int32_t c, float eps, float *y, void *stream);
 int link_ln_add_relu_backward(const float *g_y, const float *y, const float *x, const float *ln_w, int64_t n,
                               int32_t c, float eps, float *g_addend, float *g_x, float *partials, void *stream);
+/* Autocast training (ABI 13): the four training entries above with fp16 / bf16 feature rows at the kernel boundary,
+ * io_dtype = LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16 (any other value: LINK_ERR_ARG).  The 16-bit rows are widened on load
+ * and the 16-bit results rounded to nearest even on store; everything in between is fp32 as in the fp32 entries, so each
+ * gives, bit for bit, the fp32 entry's result on the widened rows, rounded once.  Non-finite values stay non-finite.
+ *   link_premix_ln_io            feats in io_dtype; w_pre, ln_w / ln_b and fin fp32.  16-bit rows: C % 16 == 0, C <= 128
+ *                                (the MFMA path; LINK_ERR_ARG otherwise); LINK_IO_F32 is link_premix_ln.
+ *   link_premix_ln_backward_io   feats (read) and g_feats (written) in io_dtype; g_fin, g_pre and partials fp32.
+ *   link_ln_add_relu_forward_io  x (the local_mix rows) in io_dtype; addend and y fp32 (autocast's LayerNorm is fp32).
+ *   link_ln_add_relu_backward_io x (read) and g_x (written) in io_dtype; g_y, y, g_addend and partials fp32. */
+int link_premix_ln_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w, const float *ln_b,
+                      int64_t n, int32_t c, float eps, float *fin, void *stream);
+int link_premix_ln_backward_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w,
+                               const float *g_fin, int64_t n, int32_t c, float eps, float *g_pre, void *g_feats,
+                               float *partials, void *stream);
+int link_ln_add_relu_forward_io(const void *x, int32_t io_dtype, const float *addend, const float *ln_w,
+                                const float *ln_b, int64_t n, int32_t c, float eps, float *y, void *stream);
+int link_ln_add_relu_backward_io(const float *g_y, const float *y, const void *x, int32_t io_dtype, const float *ln_w,
+                                 int64_t n, int32_t c, float eps, float *g_addend, void *g_x, float *partials,
+                                 void *stream);
 /* Column sums of up to three partial arrays fp[rows, cols_k] (k = 0..2; cols_k == 0 skips one) into
  * out fp[cols0+cols1+cols2], one launch, fixed summation order. */
 int link_sum_partials(const float *p0, int32_t cols0, const float *p1, int32_t cols1, const float *p2,
@@ -850,6 +869,25 @@ int link_bn_backward_reduce_relu(const float *g, const float *x, const float *me
                                  const float *weight /* NULL: 1 */, float *coef /* [3c] */, void *stream);
 int link_bn_apply_backward(const float *g, const float *x, const float *mean, const float *coef, const float *scale /* NULL: no relu */,
                            const float *shift, int64_t n, int32_t c, float *gx, void *stream);
+/* Autocast training (ABI 13): the five entries with the [N, C] rows -- x, g, y, gx -- in io_dtype (LINK_IO_F32 / LINK_IO_F16 /
+ * LINK_IO_BF16, anything else LINK_ERR_ARG), widened on load and rounded to nearest even on store.  Statistics, partials,
+ * coefficients, scale / shift and the running statistics stay fp32 (f64 partials): the fp32 entries' values on the widened
+ * rows.  A BatchNorm after a convolution sees that convolution's half rows under torch.autocast and returns its own in the
+ * same type, as torch's batch_norm does for half input with fp32 weight. */
+int link_bn_forward_stats_io(const void *x, int32_t io_dtype, int64_t n, int32_t c, float eps, float momentum, double *partial,
+                             float *mean, float *invstd, float *running_mean, float *running_var, const float *weight,
+                             const float *bias, float *scale, float *shift, void *stream);
+int link_bn_apply_forward_io(const void *x, int32_t io_dtype, const float *mean, const float *scale, const float *shift, int64_t n,
+                             int32_t c, int32_t relu, void *y, void *stream);
+int link_bn_backward_reduce_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd, int64_t n,
+                               int32_t c, double *partial, float *sum_g, float *sum_gx, const float *weight, float *coef,
+                               void *stream);
+int link_bn_backward_reduce_relu_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd,
+                                    const float *scale, const float *shift, int64_t n, int32_t c, double *partial, float *sum_g,
+                                    float *sum_gx, const float *weight, float *coef, void *stream);
+int link_bn_apply_backward_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *coef,
+                              const float *scale /* NULL: no relu */, const float *shift, int64_t n, int32_t c, void *gx,
+                              void *stream);
 
 /* =============================================================================================
  * G. One host call per LinK block on a NEW coordinate set (round 5)

@@ -19,7 +19,7 @@ OP_COS, OP_SIN, OP_COSX = 0, 1, 2
 ELK_LANE_CHANNEL, ELK_NO_PAIR, ELK_FUSED_GATHER, ELK_NO_DENSE_GRID, ELK_TILES = 1, 2, 4, 8, 16     # link_elk_desc_t::flags
 ELK_LEAN_CS, ELK_LEAN_NO_CS, ELK_LEAN_PM, ELK_LEAN_NO_PM = 32, 64, 128, 256
 IO_F32, IO_F16, IO_BF16 = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 # LINK_AMD_DEBUG=1: read the device status word back after every core call (one 32-byte D2H sync per call) and
 # raise when the index dropped a voxel -- the sync-free default trusts the caller's bounds
 DEBUG = os.environ.get("LINK_AMD_DEBUG", "0") not in ("", "0")
@@ -225,6 +225,16 @@ SIGNATURES = {
     "link_sum_partials": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p,
                                   c_void_p]),
     "link_premix_ln_backward": (c_int, [c_void_p] * 4 + [c_int64, c_int32, ctypes.c_float] + [c_void_p] * 4),
+    # autocast training (ABI 13): 16-bit rows at the boundary of the training kernels (io_dtype = IO_*)
+    "link_premix_ln_io": (c_int, [c_void_p, c_int32] + [c_void_p] * 3 + [c_int64, c_int32, c_float, c_void_p, c_void_p]),
+    "link_premix_ln_backward_io": (c_int, [c_void_p, c_int32] + [c_void_p] * 3 + [c_int64, c_int32, c_float] + [c_void_p] * 4),
+    "link_ln_add_relu_forward_io": (c_int, [c_void_p, c_int32] + [c_void_p] * 3 + [c_int64, c_int32, c_float, c_void_p, c_void_p]),
+    "link_ln_add_relu_backward_io": (c_int, [c_void_p] * 3 + [c_int32, c_void_p, c_int64, c_int32, c_float] + [c_void_p] * 4),
+    "link_bn_forward_stats_io": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_float, c_float] + [c_void_p] * 10),
+    "link_bn_apply_forward_io": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "link_bn_backward_reduce_io": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32] + [c_void_p] * 6),
+    "link_bn_backward_reduce_relu_io": (c_int, [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_int64, c_int32] + [c_void_p] * 6),
+    "link_bn_apply_backward_io": (c_int, [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_int64, c_int32, c_void_p, c_void_p]),
     "link_elk_mid_partial_rows": (c_int32, []),
     "link_dc_grid_from": (c_int64, [POINTER(LinkGrid), c_int32, POINTER(LinkDcGrid)]),
     "link_dc_premix_insert": (c_int, [c_void_p] * 5 + [c_int64, c_int32, c_float, POINTER(LinkDcGrid), c_int32] +

@@ -10,14 +10,17 @@
 //                          normalisation, unbiased for running_var)
 // Accumulation is double throughout (E[x^2] - mean^2 is then safe); a thread owns 4 consecutive channels (one 16-byte
 // load per row), the threads of a workgroup cover 256 / (C/4) rows per pass, 4 passes in flight.
+// IO (row_io.h): the type of the [N, C] rows -- x, g, the normalised output and the input gradient -- at the kernel boundary;
+// statistics, coefficients and running statistics stay fp32 / f64 (the *_io entries: autocast training, 16-bit rows).
 #include "common.h"
+#include "row_io.h"
 
 using namespace link;
 
 // RELU (backward only): the gradient arriving is that of relu(y), y = (x - mean) * scale + shift -- rows are masked by y > 0,
 // recomputed from x with the forward's own scale / shift (one multiply-add per element; no second [N, C] matrix is kept).
-template <bool BWD, bool RELU = false>
-__global__ void __launch_bounds__(256) k_col_moments(const float *__restrict__ x, const float *__restrict__ g,
+template <bool BWD, bool RELU = false, int IO = LINK_IO_F32>
+__global__ void __launch_bounds__(256) k_col_moments(const void *__restrict__ x, const void *__restrict__ g,
                                                      const float *__restrict__ mean, const float *__restrict__ invstd,
                                                      int64_t n, int c, double *__restrict__ partial,
                                                      const float *__restrict__ scale = nullptr, const float *__restrict__ shift = nullptr) {
@@ -56,15 +59,15 @@ __global__ void __launch_bounds__(256) k_col_moments(const float *__restrict__ x
       float4 v[4], gv[4];
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        v[j] = *reinterpret_cast<const float4 *>(x + (row + j * stride) * c + 4 * q);
-        gv[j] = BWD ? *reinterpret_cast<const float4 *>(g + (row + j * stride) * c + 4 * q) : v[j];
+        v[j] = row_ld4<IO>(x, (row + j * stride) * c + 4 * q);
+        gv[j] = BWD ? row_ld4<IO>(g, (row + j * stride) * c + 4 * q) : v[j];
       }
 #pragma unroll
       for (int j = 0; j < 4; j++) add(v[j], gv[j]);
     }
     for (; row < n; row += stride) {
-      const float4 v = *reinterpret_cast<const float4 *>(x + row * c + 4 * q);
-      const float4 gv = BWD ? *reinterpret_cast<const float4 *>(g + row * c + 4 * q) : v;
+      const float4 v = row_ld4<IO>(x, row * c + 4 * q);
+      const float4 gv = BWD ? row_ld4<IO>(g, row * c + 4 * q) : v;
       add(v, gv);
     }
   }
@@ -150,15 +153,15 @@ __global__ void __launch_bounds__(256) k_bn_finalize_backward(const double *__re
 // y = (x - mean) * scale + shift (centred first: no cancellation), optionally relu -- the normalisation itself, one pass.
 // BWD: grad_x = a * g' + bq * (x - mean) + cq with g' = g masked by y > 0 when the forward ended in relu (coef = a | bq | cq of
 // k_bn_finalize_backward, formed from the same masked gradient).  A thread owns 4 consecutive channels of a row.
-template <bool BWD, bool RELU>
-__global__ void __launch_bounds__(256) k_bn_apply(const float *__restrict__ x, const float *__restrict__ g, const float *__restrict__ mean,
+template <bool BWD, bool RELU, int IO = LINK_IO_F32>
+__global__ void __launch_bounds__(256) k_bn_apply(const void *__restrict__ x, const void *__restrict__ g, const float *__restrict__ mean,
                                                   const float *__restrict__ scale, const float *__restrict__ shift,
-                                                  const float *__restrict__ coef, int64_t n, int c, float *__restrict__ out) {
+                                                  const float *__restrict__ coef, int64_t n, int c, void *__restrict__ out) {
   const int cq = c >> 2;
   const int64_t total = n * cq;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int q = (int)(e % cq);
-    const float4 v = *reinterpret_cast<const float4 *>(x + 4 * e);
+    const float4 v = row_ld4<IO>(x, 4 * e);
     const float4 m = *reinterpret_cast<const float4 *>(mean + 4 * q);
     float4 o;
     if (!BWD) {
@@ -166,7 +169,7 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float *__restrict__ x, c
       o.x = fmaf(v.x - m.x, sc.x, sh.x); o.y = fmaf(v.y - m.y, sc.y, sh.y); o.z = fmaf(v.z - m.z, sc.z, sh.z); o.w = fmaf(v.w - m.w, sc.w, sh.w);
       if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
     } else {
-      float4 gv = *reinterpret_cast<const float4 *>(g + 4 * e);
+      float4 gv = row_ld4<IO>(g, 4 * e);
       if (RELU) {
         const float4 sc = *reinterpret_cast<const float4 *>(scale + 4 * q), sh = *reinterpret_cast<const float4 *>(shift + 4 * q);
         gv.x = fmaf(v.x - m.x, sc.x, sh.x) > 0.f ? gv.x : 0.f; gv.y = fmaf(v.y - m.y, sc.y, sh.y) > 0.f ? gv.y : 0.f;
@@ -177,7 +180,7 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float *__restrict__ x, c
       o.x = fmaf(v.x - m.x, bq.x, fmaf(gv.x, a.x, cq_.x)); o.y = fmaf(v.y - m.y, bq.y, fmaf(gv.y, a.y, cq_.y));
       o.z = fmaf(v.z - m.z, bq.z, fmaf(gv.z, a.z, cq_.z)); o.w = fmaf(v.w - m.w, bq.w, fmaf(gv.w, a.w, cq_.w));
     }
-    *reinterpret_cast<float4 *>(out + 4 * e) = o;
+    row_st4<IO>(out, 4 * e, o);
   }
 }
 
@@ -192,29 +195,36 @@ extern "C" int32_t link_bn_partial_workgroups(int64_t n, int32_t c) {
   return (int32_t)wgs;
 }
 
-extern "C" int link_bn_forward_stats(const float *x, int64_t n, int32_t c, float eps, float momentum, double *partial,
-                                     float *mean, float *invstd, float *running_mean, float *running_var,
-                                     const float *weight, const float *bias, float *scale, float *shift, void *stream) {
+// the launches of the five entries, one instance per row type; the fp32 entries are the IO = LINK_IO_F32 instances
+template <int IO>
+static int bn_forward_stats(const void *x, int64_t n, int32_t c, float eps, float momentum, double *partial, float *mean,
+                            float *invstd, float *running_mean, float *running_var, const float *weight, const float *bias,
+                            float *scale, float *shift, void *stream) {
   if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40)) return LINK_ERR_ARG;
   if (!x || !partial || !mean || !invstd || (scale == nullptr) != (shift == nullptr)) return LINK_ERR_ARG;
   const int wgs = link_bn_partial_workgroups(n, c);
   hipStream_t st = S(stream);
-  hipLaunchKernelGGL(k_col_moments<false>, dim3(wgs), dim3(256), 0, st, x, nullptr, nullptr, nullptr, n, (int)c, partial);
+  hipLaunchKernelGGL((k_col_moments<false, false, IO>), dim3(wgs), dim3(256), 0, st, x, nullptr, nullptr, nullptr, n, (int)c, partial,
+                     nullptr, nullptr);
   hipLaunchKernelGGL(k_bn_finalize_forward, dim3((c + 15) / 16), dim3(256), 0, st, partial, wgs, n, (int)c, eps, momentum, mean,
                      invstd, running_mean, running_var, weight, bias, scale, shift);
   return check_launch("link_bn_forward_stats");
 }
 
-extern "C" int link_bn_backward_reduce(const float *g, const float *x, const float *mean, const float *invstd, int64_t n,
-                                       int32_t c, double *partial, float *sum_g, float *sum_gx, const float *weight,
-                                       float *coef, void *stream) {
+template <int IO>
+static int bn_backward_reduce(const void *g, const void *x, const float *mean, const float *invstd, const float *scale,
+                              const float *shift, int64_t n, int32_t c, double *partial, float *sum_g, float *sum_gx,
+                              const float *weight, float *coef, bool relu, void *stream) {
   if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40)) return LINK_ERR_ARG;
-  if (!g || !x || !mean || !invstd || !partial || !sum_g || !sum_gx) return LINK_ERR_ARG;
+  if (!g || !x || !mean || !invstd || !partial || !sum_g || !sum_gx || (relu && (!scale || !shift))) return LINK_ERR_ARG;
   const int wgs = link_bn_partial_workgroups(n, c);
   hipStream_t st = S(stream);
-  hipLaunchKernelGGL(k_col_moments<true>, dim3(wgs), dim3(256), 0, st, x, g, mean, invstd, n, (int)c, partial);
+  if (relu)
+    hipLaunchKernelGGL((k_col_moments<true, true, IO>), dim3(wgs), dim3(256), 0, st, x, g, mean, invstd, n, (int)c, partial, scale, shift);
+  else
+    hipLaunchKernelGGL((k_col_moments<true, false, IO>), dim3(wgs), dim3(256), 0, st, x, g, mean, invstd, n, (int)c, partial, nullptr, nullptr);
   hipLaunchKernelGGL(k_bn_finalize_backward, dim3((c + 15) / 16), dim3(256), 0, st, partial, wgs, (int)c, sum_g, sum_gx, weight, mean, invstd, n, coef);
-  return check_launch("link_bn_backward_reduce");
+  return check_launch(relu ? "link_bn_backward_reduce_relu" : "link_bn_backward_reduce");
 }
 
 static unsigned bn_apply_grid(int64_t n, int32_t c) {
@@ -222,33 +232,102 @@ static unsigned bn_apply_grid(int64_t n, int32_t c) {
   return (unsigned)(wgs < 1 ? 1 : (wgs > 4096 ? 4096 : wgs));
 }
 
-extern "C" int link_bn_apply_forward(const float *x, const float *mean, const float *scale, const float *shift, int64_t n, int32_t c,
-                                     int32_t relu, float *y, void *stream) {
+template <int IO>
+static int bn_apply_forward(const void *x, const float *mean, const float *scale, const float *shift, int64_t n, int32_t c,
+                            int32_t relu, void *y, void *stream) {
   if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40) || !x || !mean || !scale || !shift || !y) return LINK_ERR_ARG;
   hipStream_t st = S(stream);
-  if (relu) hipLaunchKernelGGL((k_bn_apply<false, true>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, nullptr, mean, scale, shift, nullptr, n, (int)c, y);
-  else hipLaunchKernelGGL((k_bn_apply<false, false>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, nullptr, mean, scale, shift, nullptr, n, (int)c, y);
+  if (relu) hipLaunchKernelGGL((k_bn_apply<false, true, IO>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, nullptr, mean, scale, shift, nullptr, n, (int)c, y);
+  else hipLaunchKernelGGL((k_bn_apply<false, false, IO>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, nullptr, mean, scale, shift, nullptr, n, (int)c, y);
   return check_launch("link_bn_apply_forward");
+}
+
+template <int IO>
+static int bn_apply_backward(const void *g, const void *x, const float *mean, const float *coef, const float *scale,
+                             const float *shift, int64_t n, int32_t c, void *gx, void *stream) {
+  if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40) || !g || !x || !mean || !coef || !gx) return LINK_ERR_ARG;
+  if ((scale == nullptr) != (shift == nullptr)) return LINK_ERR_ARG;
+  hipStream_t st = S(stream);
+  if (scale) hipLaunchKernelGGL((k_bn_apply<true, true, IO>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, g, mean, scale, shift, coef, n, (int)c, gx);
+  else hipLaunchKernelGGL((k_bn_apply<true, false, IO>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, g, mean, nullptr, nullptr, coef, n, (int)c, gx);
+  return check_launch("link_bn_apply_backward");
+}
+
+extern "C" int link_bn_forward_stats(const float *x, int64_t n, int32_t c, float eps, float momentum, double *partial,
+                                     float *mean, float *invstd, float *running_mean, float *running_var,
+                                     const float *weight, const float *bias, float *scale, float *shift, void *stream) {
+  return bn_forward_stats<LINK_IO_F32>(x, n, c, eps, momentum, partial, mean, invstd, running_mean, running_var, weight, bias,
+                                       scale, shift, stream);
+}
+
+extern "C" int link_bn_backward_reduce(const float *g, const float *x, const float *mean, const float *invstd, int64_t n,
+                                       int32_t c, double *partial, float *sum_g, float *sum_gx, const float *weight,
+                                       float *coef, void *stream) {
+  return bn_backward_reduce<LINK_IO_F32>(g, x, mean, invstd, nullptr, nullptr, n, c, partial, sum_g, sum_gx, weight, coef, false,
+                                         stream);
+}
+
+extern "C" int link_bn_apply_forward(const float *x, const float *mean, const float *scale, const float *shift, int64_t n, int32_t c,
+                                     int32_t relu, float *y, void *stream) {
+  return bn_apply_forward<LINK_IO_F32>(x, mean, scale, shift, n, c, relu, y, stream);
 }
 
 extern "C" int link_bn_backward_reduce_relu(const float *g, const float *x, const float *mean, const float *invstd, const float *scale,
                                             const float *shift, int64_t n, int32_t c, double *partial, float *sum_g, float *sum_gx,
                                             const float *weight, float *coef, void *stream) {
-  if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40)) return LINK_ERR_ARG;
-  if (!g || !x || !mean || !invstd || !scale || !shift || !partial || !sum_g || !sum_gx) return LINK_ERR_ARG;
-  const int wgs = link_bn_partial_workgroups(n, c);
-  hipStream_t st = S(stream);
-  hipLaunchKernelGGL((k_col_moments<true, true>), dim3(wgs), dim3(256), 0, st, x, g, mean, invstd, n, (int)c, partial, scale, shift);
-  hipLaunchKernelGGL(k_bn_finalize_backward, dim3((c + 15) / 16), dim3(256), 0, st, partial, wgs, (int)c, sum_g, sum_gx, weight, mean, invstd, n, coef);
-  return check_launch("link_bn_backward_reduce_relu");
+  return bn_backward_reduce<LINK_IO_F32>(g, x, mean, invstd, scale, shift, n, c, partial, sum_g, sum_gx, weight, coef, true, stream);
 }
 
 extern "C" int link_bn_apply_backward(const float *g, const float *x, const float *mean, const float *coef, const float *scale,
                                       const float *shift, int64_t n, int32_t c, float *gx, void *stream) {
-  if (n < 1 || !bn_width_ok(c) || n * (int64_t)c >= (1LL << 40) || !g || !x || !mean || !coef || !gx) return LINK_ERR_ARG;
-  if ((scale == nullptr) != (shift == nullptr)) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  if (scale) hipLaunchKernelGGL((k_bn_apply<true, true>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, g, mean, scale, shift, coef, n, (int)c, gx);
-  else hipLaunchKernelGGL((k_bn_apply<true, false>), dim3(bn_apply_grid(n, c)), dim3(256), 0, st, x, g, mean, nullptr, nullptr, coef, n, (int)c, gx);
-  return check_launch("link_bn_apply_backward");
+  return bn_apply_backward<LINK_IO_F32>(g, x, mean, coef, scale, shift, n, c, gx, stream);
 }
+
+// 16-bit rows (io_dtype = LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16 for x, g, y, gx): the same kernels with the rows widened on
+// load and rounded (RNE) on store -- autocast training, where a BatchNorm sees the half rows of the convolution before it
+#define LINK_BN_IO(CALL)                                               \
+  switch (io_dtype) {                                                  \
+    case LINK_IO_F32: return CALL(LINK_IO_F32);                        \
+    case LINK_IO_F16: return CALL(LINK_IO_F16);                        \
+    case LINK_IO_BF16: return CALL(LINK_IO_BF16);                      \
+    default: return LINK_ERR_ARG;                                      \
+  }
+
+extern "C" int link_bn_forward_stats_io(const void *x, int32_t io_dtype, int64_t n, int32_t c, float eps, float momentum,
+                                        double *partial, float *mean, float *invstd, float *running_mean, float *running_var,
+                                        const float *weight, const float *bias, float *scale, float *shift, void *stream) {
+#define LINK_C(IO) bn_forward_stats<IO>(x, n, c, eps, momentum, partial, mean, invstd, running_mean, running_var, weight, bias, scale, shift, stream)
+  LINK_BN_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_bn_apply_forward_io(const void *x, int32_t io_dtype, const float *mean, const float *scale, const float *shift,
+                                        int64_t n, int32_t c, int32_t relu, void *y, void *stream) {
+#define LINK_C(IO) bn_apply_forward<IO>(x, mean, scale, shift, n, c, relu, y, stream)
+  LINK_BN_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_bn_backward_reduce_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd,
+                                          int64_t n, int32_t c, double *partial, float *sum_g, float *sum_gx, const float *weight,
+                                          float *coef, void *stream) {
+#define LINK_C(IO) bn_backward_reduce<IO>(g, x, mean, invstd, nullptr, nullptr, n, c, partial, sum_g, sum_gx, weight, coef, false, stream)
+  LINK_BN_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_bn_backward_reduce_relu_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd,
+                                               const float *scale, const float *shift, int64_t n, int32_t c, double *partial,
+                                               float *sum_g, float *sum_gx, const float *weight, float *coef, void *stream) {
+#define LINK_C(IO) bn_backward_reduce<IO>(g, x, mean, invstd, scale, shift, n, c, partial, sum_g, sum_gx, weight, coef, true, stream)
+  LINK_BN_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_bn_apply_backward_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *coef,
+                                         const float *scale, const float *shift, int64_t n, int32_t c, void *gx, void *stream) {
+#define LINK_C(IO) bn_apply_backward<IO>(g, x, mean, coef, scale, shift, n, c, gx, stream)
+  LINK_BN_IO(LINK_C)
+#undef LINK_C
+}
+#undef LINK_BN_IO

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "dense_common.h"
+#include "row_io.h"
 
 namespace DC_IO_NS {
 using namespace link;
@@ -49,11 +50,7 @@ __device__ __forceinline__ float4 io_ldb4(__amdgpu_buffer_rsrc_t r, uint32_t row
     }
   }
 }
-__device__ __forceinline__ unsigned bf16_rne(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;      // NaN stays NaN
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
+// bf16_rne (round to nearest even, NaN kept): row_io.h
 // four channels as 16-bit elements of the boundary type (IO = 1, 2)
 __device__ __forceinline__ v2i_t io_pack4(float4 v) {
   v2i_t x;

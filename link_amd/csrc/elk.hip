@@ -23,6 +23,7 @@
 #include <limits.h>
 
 #include "elk_common.h"
+#include "row_io.h"
 
 using namespace link;
 
@@ -36,8 +37,9 @@ static bool g_wt_fwd();
 // software pipelining at all -- a wave is load -> 64 MFMA -> LayerNorm -> store per tile, and 5-6
 // resident waves per SIMD overlap each other's phases (register rotation / predication defeat the
 // compiler's counted waits on this target, occupancy does not).
-template <int C>
-__global__ void __launch_bounds__(256) k_premix_ln_tlp(const float *__restrict__ feats,
+// IO (row_io.h): type of the feats rows (fp32, or fp16 / bf16 widened on load: link_premix_ln_io); fin stays fp32.
+template <int C, int IO = LINK_IO_F32>
+__global__ void __launch_bounds__(256) k_premix_ln_tlp(const void *__restrict__ feats,
                                                        const float *__restrict__ w_pre,
                                                        const float *__restrict__ ln_w,
                                                        const float *__restrict__ ln_b, int64_t n,
@@ -60,7 +62,7 @@ __global__ void __launch_bounds__(256) k_premix_ln_tlp(const float *__restrict__
     const int64_t vl = ok ? v : n - 1;
     float4 f[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) f[t] = *reinterpret_cast<const float4 *>(&feats[vl * C + 16 * t + 4 * g]);
+    for (int t = 0; t < T; t++) f[t] = row_ld4<IO>(feats, vl * C + 16 * t + 4 * g);
     floatx4 acc[T];
 #pragma unroll
     for (int tp = 0; tp < T; tp++) acc[tp] = (floatx4){0.f, 0.f, 0.f, 0.f};
@@ -108,8 +110,8 @@ __global__ void __launch_bounds__(256) k_premix_ln_tlp(const float *__restrict__
   }
 }
 
-template <int C>
-static int launch_premix_tlp(const float *feats, const float *w_pre, const float *ln_w, const float *ln_b,
+template <int C, int IO = LINK_IO_F32>
+static int launch_premix_tlp(const void *feats, const float *w_pre, const float *ln_w, const float *ln_b,
                              int64_t n, float eps, float *fin, hipStream_t st) {
   size_t lds = (size_t)C * (C + 4) * sizeof(float);
   int64_t tiles = (n + 15) / 16;
@@ -118,10 +120,10 @@ static int launch_premix_tlp(const float *feats, const float *w_pre, const float
   if (lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in once per kernel (160 KB per CU on gfx950)
     // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
     // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_tlp<C>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_tlp<C, IO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  hipLaunchKernelGGL(k_premix_ln_tlp<C>, dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, ln_b, n,
+  hipLaunchKernelGGL((k_premix_ln_tlp<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, ln_b, n,
                      eps, fin, g_wt_fwd() && wt_ok(n, C));
   return check_launch("link_premix_ln");
 }
@@ -2073,12 +2075,13 @@ static void launch_out_ln_bwd(const link_elk_desc_t &d, int wgs, hipStream_t st,
 // operand is a transposed copy of W in LDS.  g_pre is also stored (the weight gradient
 // g_pre^T @ F is a plain GEMM left to the library), and per-workgroup partial sums of
 // d/d(pre_mix.1.weight) = sum g_fin*xhat and d/d(pre_mix.1.bias) = sum g_fin are written.
-template <int C>
-__global__ void __launch_bounds__(256) k_premix_ln_bwd(const float *__restrict__ feats,
+// IO (row_io.h): type of feats (read) and g_feats (written); g_fin, g_pre and the partials stay fp32.
+template <int C, int IO = LINK_IO_F32>
+__global__ void __launch_bounds__(256) k_premix_ln_bwd(const void *__restrict__ feats,
                                                        const float *__restrict__ w_pre,
                                                        const float *__restrict__ ln_w,
                                                        const float *__restrict__ g_fin, int64_t n, float eps,
-                                                       float *__restrict__ g_pre, float *__restrict__ g_feats,
+                                                       float *__restrict__ g_pre, void *__restrict__ g_feats,
                                                        float *__restrict__ partials) {
   constexpr int T = C / 16;
   constexpr int LDW = C + 4;
@@ -2114,7 +2117,7 @@ __global__ void __launch_bounds__(256) k_premix_ln_bwd(const float *__restrict__
     const int64_t vl = ok ? v : n - 1;
     float4 f[T], gf4[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) f[t] = *reinterpret_cast<const float4 *>(&feats[vl * C + 16 * t + 4 * g]);
+    for (int t = 0; t < T; t++) f[t] = row_ld4<IO>(feats, vl * C + 16 * t + 4 * g);
 #pragma unroll
     for (int t = 0; t < T; t++) gf4[t] = *reinterpret_cast<const float4 *>(&g_fin[vl * C + 16 * t + 4 * g]);
     floatx4 acc[T];
@@ -2191,7 +2194,7 @@ __global__ void __launch_bounds__(256) k_premix_ln_bwd(const float *__restrict__
     if (ok) {
 #pragma unroll
       for (int tp = 0; tp < T; tp++)
-        *reinterpret_cast<float4 *>(&g_feats[v * C + 16 * tp + 4 * g]) = make_float4(acc2[tp][0], acc2[tp][1], acc2[tp][2], acc2[tp][3]);
+        row_st4<IO>(g_feats, v * C + 16 * tp + 4 * g, make_float4(acc2[tp][0], acc2[tp][1], acc2[tp][2], acc2[tp][3]));
     }
   }
   // LayerNorm parameter gradients: sum over the 16 voxel lanes of each quarter-wave, then over waves
@@ -2219,18 +2222,18 @@ __global__ void __launch_bounds__(256) k_premix_ln_bwd(const float *__restrict__
   }
 }
 
-template <int C>
-static int launch_premix_bwd(const float *feats, const float *w_pre, const float *ln_w, const float *g_fin,
-                             int64_t n, float eps, float *g_pre, float *g_feats, float *partials, int wgs,
+template <int C, int IO = LINK_IO_F32>
+static int launch_premix_bwd(const void *feats, const float *w_pre, const float *ln_w, const float *g_fin,
+                             int64_t n, float eps, float *g_pre, void *g_feats, float *partials, int wgs,
                              hipStream_t st) {
   size_t lds = ((size_t)2 * C * (C + 4) + 8 * C) * sizeof(float);
   if (lds > 64 * 1024) {
     // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
     // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_bwd<C>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_bwd<C, IO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  hipLaunchKernelGGL(k_premix_ln_bwd<C>, dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, g_fin, n, eps,
+  hipLaunchKernelGGL((k_premix_ln_bwd<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, g_fin, n, eps,
                      g_pre, g_feats, partials);
   return check_launch("link_premix_ln_backward");
 }
@@ -2284,8 +2287,9 @@ extern "C" int link_elk_out_ln_backward(const float *g_out, const float *A, cons
 // forward and backward, one 16-byte-per-lane group per row (persistent grid).  Inference fuses this
 // tail into the convolution kernel instead (conv.hip, row N2).
 // ---------------------------------------------------------------------------------------------
-template <int LPR>
-__global__ void __launch_bounds__(256) k_ln_add_relu_fwd_g(const float *__restrict__ x,
+// IO (row_io.h): type of the x rows (the local_mix output; link_ln_add_relu_*_io); addend, y and g_y stay fp32.
+template <int LPR, int IO = LINK_IO_F32>
+__global__ void __launch_bounds__(256) k_ln_add_relu_fwd_g(const void *__restrict__ x,
                                                            const float *__restrict__ addend,
                                                            const float *__restrict__ ln_w,
                                                            const float *__restrict__ ln_b, int64_t n, int c,
@@ -2299,7 +2303,7 @@ __global__ void __launch_bounds__(256) k_ln_add_relu_fwd_g(const float *__restri
   const float4 w4 = *reinterpret_cast<const float4 *>(&ln_w[cofs]), b4 = *reinterpret_cast<const float4 *>(&ln_b[cofs]);
   const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
   for (int64_t i = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; i < n; i += ngroups) {
-    float4 v = *reinterpret_cast<const float4 *>(&x[i * c + cofs]);
+    float4 v = row_ld4<IO>(x, i * c + cofs);
     const float4 a = *reinterpret_cast<const float4 *>(&addend[i * c + cofs]);
     if (!act) v = make_float4(0.f, 0.f, 0.f, 0.f);
     const float mean = grp_sum<LPR>((v.x + v.y) + (v.z + v.w)) * inv_c;
@@ -2316,13 +2320,13 @@ __global__ void __launch_bounds__(256) k_ln_add_relu_fwd_g(const float *__restri
   }
 }
 
-template <int LPR>
+template <int LPR, int IO = LINK_IO_F32>
 __global__ void __launch_bounds__(256) k_ln_add_relu_bwd_g(const float *__restrict__ g_y,
                                                            const float *__restrict__ y,
-                                                           const float *__restrict__ x,
+                                                           const void *__restrict__ x,
                                                            const float *__restrict__ ln_w, int64_t n, int c,
                                                            float eps, float *__restrict__ g_addend,
-                                                           float *__restrict__ g_x, float *__restrict__ partials) {
+                                                           void *__restrict__ g_x, float *__restrict__ partials) {
   constexpr int G = 64 / LPR;
   __shared__ float red[4][8][LPR];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2335,7 +2339,7 @@ __global__ void __launch_bounds__(256) k_ln_add_relu_bwd_g(const float *__restri
   float aw[4] = {0.f, 0.f, 0.f, 0.f}, ab[4] = {0.f, 0.f, 0.f, 0.f};
   const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
   for (int64_t i = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; i < n; i += ngroups) {
-    const float4 v4 = *reinterpret_cast<const float4 *>(&x[i * c + cofs]);
+    const float4 v4 = row_ld4<IO>(x, i * c + cofs);
     const float4 y4 = *reinterpret_cast<const float4 *>(&y[i * c + cofs]);
     const float4 g4 = *reinterpret_cast<const float4 *>(&g_y[i * c + cofs]);
     const float xv[4] = {v4.x, v4.y, v4.z, v4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
@@ -2361,9 +2365,9 @@ __global__ void __launch_bounds__(256) k_ln_add_relu_bwd_g(const float *__restri
     const float m1 = grp_sum<LPR>(s1) * inv_c, m2 = grp_sum<LPR>(s2) * inv_c;
     if (act) {
       *reinterpret_cast<float4 *>(&g_addend[i * c + ch0]) = make_float4(g[0], g[1], g[2], g[3]);
-      *reinterpret_cast<float4 *>(&g_x[i * c + ch0]) =
-          make_float4(rstd * (gx[0] - m1 - xh[0] * m2), rstd * (gx[1] - m1 - xh[1] * m2),
-                      rstd * (gx[2] - m1 - xh[2] * m2), rstd * (gx[3] - m1 - xh[3] * m2));
+      row_st4<IO>(g_x, i * c + ch0,
+                  make_float4(rstd * (gx[0] - m1 - xh[0] * m2), rstd * (gx[1] - m1 - xh[1] * m2),
+                              rstd * (gx[2] - m1 - xh[2] * m2), rstd * (gx[3] - m1 - xh[3] * m2)));
     }
   }
 #pragma unroll
@@ -2389,41 +2393,137 @@ __global__ void __launch_bounds__(256) k_ln_add_relu_bwd_g(const float *__restri
 
 extern "C" int32_t link_elk_mid_partial_rows(void);
 
-extern "C" int link_ln_add_relu_forward(const float *x, const float *addend, const float *ln_w,
-                                        const float *ln_b, int64_t n, int32_t c, float eps, float *y,
-                                        void *stream) {
+template <int IO>
+static int ln_add_relu_forward(const void *x, const float *addend, const float *ln_w, const float *ln_b, int64_t n, int32_t c,
+                               float eps, float *y, void *stream) {
   if (n < 0 || c <= 0 || (c & 3) != 0 || c > 256) return LINK_ERR_ARG;
   if (n == 0) return LINK_OK;
   if (!x || !addend || !ln_w || !ln_b || !y) return LINK_ERR_ARG;
   dim3 grid(1024), block(256);
   hipStream_t st = S(stream);
   switch (lanes_per_row(c)) {
-    case 1: case 2: case 4: hipLaunchKernelGGL(k_ln_add_relu_fwd_g<4>, grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 8: hipLaunchKernelGGL(k_ln_add_relu_fwd_g<8>, grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 16: hipLaunchKernelGGL(k_ln_add_relu_fwd_g<16>, grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 32: hipLaunchKernelGGL(k_ln_add_relu_fwd_g<32>, grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    default: hipLaunchKernelGGL(k_ln_add_relu_fwd_g<64>, grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
+    case 1: case 2: case 4: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<4, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
+    case 8: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<8, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
+    case 16: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<16, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
+    case 32: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<32, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
+    default: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<64, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
   }
   return check_launch("link_ln_add_relu_forward");
 }
 
-extern "C" int link_ln_add_relu_backward(const float *g_y, const float *y, const float *x, const float *ln_w,
-                                         int64_t n, int32_t c, float eps, float *g_addend, float *g_x,
-                                         float *partials, void *stream) {
+template <int IO>
+static int ln_add_relu_backward(const float *g_y, const float *y, const void *x, const float *ln_w, int64_t n, int32_t c,
+                                float eps, float *g_addend, void *g_x, float *partials, void *stream) {
   if (n < 0 || c <= 0 || (c & 3) != 0 || c > 256) return LINK_ERR_ARG;
   if (!partials) return LINK_ERR_ARG;
   if (n > 0 && (!g_y || !y || !x || !ln_w || !g_addend || !g_x)) return LINK_ERR_ARG;
   dim3 grid(link_elk_mid_partial_rows()), block(256);
   hipStream_t st = S(stream);
   switch (lanes_per_row(c)) {
-    case 1: case 2: case 4: hipLaunchKernelGGL(k_ln_add_relu_bwd_g<4>, grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 8: hipLaunchKernelGGL(k_ln_add_relu_bwd_g<8>, grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 16: hipLaunchKernelGGL(k_ln_add_relu_bwd_g<16>, grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 32: hipLaunchKernelGGL(k_ln_add_relu_bwd_g<32>, grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    default: hipLaunchKernelGGL(k_ln_add_relu_bwd_g<64>, grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
+    case 1: case 2: case 4: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<4, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
+    case 8: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<8, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
+    case 16: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<16, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
+    case 32: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<32, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
+    default: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<64, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
   }
   return check_launch("link_ln_add_relu_backward");
 }
+
+extern "C" int link_ln_add_relu_forward(const float *x, const float *addend, const float *ln_w,
+                                        const float *ln_b, int64_t n, int32_t c, float eps, float *y,
+                                        void *stream) {
+  return ln_add_relu_forward<LINK_IO_F32>(x, addend, ln_w, ln_b, n, c, eps, y, stream);
+}
+
+extern "C" int link_ln_add_relu_backward(const float *g_y, const float *y, const float *x, const float *ln_w,
+                                         int64_t n, int32_t c, float eps, float *g_addend, float *g_x,
+                                         float *partials, void *stream) {
+  return ln_add_relu_backward<LINK_IO_F32>(g_y, y, x, ln_w, n, c, eps, g_addend, g_x, partials, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 16-bit rows for autocast training (io_dtype = LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16): the kernels above instantiated per
+// row type (row_io.h) -- feats / x read, g_feats / g_x written in io_dtype, everything else fp32 as in the fp32 entries.
+// ---------------------------------------------------------------------------------------------
+#define LINK_ROW_IO(CALL)                                              \
+  switch (io_dtype) {                                                  \
+    case LINK_IO_F32: return CALL(LINK_IO_F32);                        \
+    case LINK_IO_F16: return CALL(LINK_IO_F16);                        \
+    case LINK_IO_BF16: return CALL(LINK_IO_BF16);                      \
+    default: return LINK_ERR_ARG;                                      \
+  }
+
+template <int IO>
+static int premix_ln_io(const void *feats, const float *w_pre, const float *ln_w, const float *ln_b, int64_t n, int32_t c,
+                        float eps, float *fin, hipStream_t st) {
+  switch (c) {
+    case 16: return launch_premix_tlp<16, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 32: return launch_premix_tlp<32, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 48: return launch_premix_tlp<48, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 64: return launch_premix_tlp<64, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 80: return launch_premix_tlp<80, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 96: return launch_premix_tlp<96, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    case 112: return launch_premix_tlp<112, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    default: return launch_premix_tlp<128, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+  }
+}
+
+extern "C" int link_premix_ln_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w, const float *ln_b,
+                                 int64_t n, int32_t c, float eps, float *fin, void *stream) {
+  if (!row_io_ok(io_dtype)) return LINK_ERR_ARG;
+  if (io_dtype == LINK_IO_F32) return link_premix_ln(reinterpret_cast<const float *>(feats), w_pre, ln_w, ln_b, n, c, eps, fin, stream);
+  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;     // 16-bit rows: the MFMA widths only
+  if (n == 0) return LINK_OK;
+  if (!feats || !w_pre || !ln_w || !ln_b || !fin) return LINK_ERR_ARG;
+  hipStream_t st = S(stream);
+  if (io_dtype == LINK_IO_F16) return premix_ln_io<LINK_IO_F16>(feats, w_pre, ln_w, ln_b, n, c, eps, fin, st);
+  return premix_ln_io<LINK_IO_BF16>(feats, w_pre, ln_w, ln_b, n, c, eps, fin, st);
+}
+
+template <int IO>
+static int premix_ln_backward_io(const void *feats, const float *w_pre, const float *ln_w, const float *g_fin, int64_t n, int32_t c,
+                                 float eps, float *g_pre, void *g_feats, float *partials, hipStream_t st) {
+  const int wgs = link_elk_mid_partial_rows();
+  switch (c) {
+    case 16: return launch_premix_bwd<16, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 32: return launch_premix_bwd<32, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 48: return launch_premix_bwd<48, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 64: return launch_premix_bwd<64, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 80: return launch_premix_bwd<80, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 96: return launch_premix_bwd<96, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    case 112: return launch_premix_bwd<112, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+    default: return launch_premix_bwd<128, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
+  }
+}
+
+extern "C" int link_premix_ln_backward_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w,
+                                          const float *g_fin, int64_t n, int32_t c, float eps, float *g_pre, void *g_feats,
+                                          float *partials, void *stream) {
+  if (!row_io_ok(io_dtype)) return LINK_ERR_ARG;
+  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;
+  if (n == 0) return LINK_OK;
+  if (!feats || !w_pre || !ln_w || !g_fin || !g_pre || !g_feats || !partials) return LINK_ERR_ARG;
+  hipStream_t st = S(stream);
+#define LINK_C(IO) premix_ln_backward_io<IO>(feats, w_pre, ln_w, g_fin, n, c, eps, g_pre, g_feats, partials, st)
+  LINK_ROW_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_ln_add_relu_forward_io(const void *x, int32_t io_dtype, const float *addend, const float *ln_w,
+                                           const float *ln_b, int64_t n, int32_t c, float eps, float *y, void *stream) {
+#define LINK_C(IO) ln_add_relu_forward<IO>(x, addend, ln_w, ln_b, n, c, eps, y, stream)
+  LINK_ROW_IO(LINK_C)
+#undef LINK_C
+}
+
+extern "C" int link_ln_add_relu_backward_io(const float *g_y, const float *y, const void *x, int32_t io_dtype, const float *ln_w,
+                                            int64_t n, int32_t c, float eps, float *g_addend, void *g_x, float *partials,
+                                            void *stream) {
+#define LINK_C(IO) ln_add_relu_backward<IO>(g_y, y, x, ln_w, n, c, eps, g_addend, g_x, partials, stream)
+  LINK_ROW_IO(LINK_C)
+#undef LINK_C
+}
+#undef LINK_ROW_IO
 
 // Column sums of up to three per-workgroup partial arrays [rows, cols_k] in one launch, fixed order
 // (row lanes ascending, then a fixed LDS tree): the deterministic tail of every parameter gradient.

@@ -848,7 +848,13 @@ def _weight_grad(g_pre: torch.Tensor, feats: torch.Tensor) -> torch.Tensor:
 class _ElkCoreTrain(torch.autograd.Function):
     """Whole R_core (pre_mix -> ... -> self.norm) with a hand-written backward: forward = the inference
     kernels (+ saved A, den, fin); backward = link_elk_out_ln_backward -> link_elk_mid_backward ->
-    link_premix_ln_backward (six kernels), the weight gradient through one batched library GEMM."""
+    link_premix_ln_backward (six kernels), the weight gradient through one batched library GEMM.
+
+    fp16 / bf16 feats (autocast training; fp32 parameters): pre_mix reads the 16-bit rows as they are
+    (link_premix_ln_io) and only those rows are saved; the output stays fp32 (what self.norm returns under
+    autocast) and g_feats comes back in the row type (link_premix_ln_backward_io).  Every value equals the fp32
+    path's on the widened rows, g_feats rounded once.  The pre_mix weight gradient stays the batched library GEMM
+    over the widened rows."""
 
     @staticmethod
     def forward(ctx, feats, w_pre, pre_ln_w, pre_ln_b, w_pos, alpha, ln_w, ln_b, index: BlockIndex, op: int,
@@ -856,7 +862,9 @@ class _ElkCoreTrain(torch.autograd.Function):
         n, c = feats.shape
         dev = feats.device
         lib, st = L.lib(), _st()
-        feats = feats.detach().contiguous().float()
+        io = _IO_DTYPES.get(feats.dtype, L.IO_F32)
+        feats = feats.detach().contiguous()
+        feats = feats if io != L.IO_F32 else feats.float()      # 16-bit rows stay 16-bit: widened inside the kernels
         f32 = lambda t: t.detach().contiguous().float()
         w_pre_c, pre_w, pre_b, w_pos_c, ln_w_c, ln_b_c = map(f32, (w_pre, pre_ln_w, pre_ln_b, w_pos, ln_w, ln_b))
         al = f32(alpha).view(-1) if alpha is not None else None
@@ -868,8 +876,12 @@ class _ElkCoreTrain(torch.autograd.Function):
         A = torch.empty((m_cap, parts * c), dtype=torch.float32, device=dev)
         den = torch.empty(m_cap, dtype=torch.float32, device=dev)
         out = _alloc_out(index, (n, c), dev)
-        L.check(lib.link_premix_ln(feats.data_ptr(), w_pre_c.data_ptr(), pre_w.data_ptr(), pre_b.data_ptr(), n, c,
-                                   float(eps), fin.data_ptr(), st), "link_premix_ln")
+        if io == L.IO_F32:
+            L.check(lib.link_premix_ln(feats.data_ptr(), w_pre_c.data_ptr(), pre_w.data_ptr(), pre_b.data_ptr(), n, c,
+                                       float(eps), fin.data_ptr(), st), "link_premix_ln")
+        else:
+            L.check(lib.link_premix_ln_io(feats.data_ptr(), io, w_pre_c.data_ptr(), pre_w.data_ptr(), pre_b.data_ptr(), n, c,
+                                          float(eps), fin.data_ptr(), st), "link_premix_ln_io")
         L.check(lib.link_elk_mid_forward(
             fin.data_ptr(), index.vox_sorted.data_ptr(), index.pos_blk.data_ptr(), index.blk_start.data_ptr(),
             index.blk_coords.data_ptr(), index.cell_blk.data_ptr(), ctypes.byref(index.grid),
@@ -893,8 +905,10 @@ class _ElkCoreTrain(torch.autograd.Function):
         g = g.contiguous().float()
         rows = int(lib.link_elk_mid_partial_rows())
         alp = al.data_ptr() if al is not None else None
-        work = torch.empty((3, n, c), dtype=torch.float32, device=dev)      # g_new (later g_pre) | g_fin | g_feats
-        g_new, g_fin, g_feats = work[0], work[1], work[2]
+        io = _IO_DTYPES[feats.dtype]
+        work = torch.empty((3 if io == L.IO_F32 else 2, n, c), dtype=torch.float32, device=dev)   # g_new (later g_pre) | g_fin | g_feats
+        g_new, g_fin = work[0], work[1]
+        g_feats = work[2] if io == L.IO_F32 else torch.empty((n, c), dtype=feats.dtype, device=dev)
         part = torch.empty(rows * 8 * c + 8 * c, dtype=torch.float32, device=dev)
         part_o, part_m, part_p = part[: rows * 2 * c], part[rows * 2 * c: rows * 6 * c], part[rows * 6 * c: rows * 8 * c]
         tot = part[rows * 8 * c:]
@@ -910,13 +924,18 @@ class _ElkCoreTrain(torch.autograd.Function):
             ctypes.byref(desc), n, m_cap, ctx.S.data_ptr(), gS.data_ptr(), g_fin.data_ptr(), part_m.data_ptr(),
             st), "link_elk_mid_backward")
         g_pre = g_new                                   # g_new is dead from here on: reuse its storage
-        L.check(lib.link_premix_ln_backward(feats.data_ptr(), w_pre_c.data_ptr(), pre_w.data_ptr(),
-                                            g_fin.data_ptr(), n, c, float(eps), g_pre.data_ptr(),
-                                            g_feats.data_ptr(), part_p.data_ptr(), st), "link_premix_ln_backward")
+        if io == L.IO_F32:
+            L.check(lib.link_premix_ln_backward(feats.data_ptr(), w_pre_c.data_ptr(), pre_w.data_ptr(),
+                                                g_fin.data_ptr(), n, c, float(eps), g_pre.data_ptr(),
+                                                g_feats.data_ptr(), part_p.data_ptr(), st), "link_premix_ln_backward")
+        else:
+            L.check(lib.link_premix_ln_backward_io(feats.data_ptr(), io, w_pre_c.data_ptr(), pre_w.data_ptr(),
+                                                   g_fin.data_ptr(), n, c, float(eps), g_pre.data_ptr(),
+                                                   g_feats.data_ptr(), part_p.data_ptr(), st), "link_premix_ln_backward_io")
         L.check(lib.link_sum_partials(part_o.data_ptr(), 2 * c, part_m.data_ptr(), 4 * c, part_p.data_ptr(), 2 * c,
                                       rows, tot.data_ptr(), st), "link_sum_partials")
         sh = ctx.shapes
-        g_w_pre = _weight_grad(g_pre, feats).view(sh[0])
+        g_w_pre = _weight_grad(g_pre, feats if io == L.IO_F32 else feats.float()).view(sh[0])
         th = tot[2 * c: 6 * c].view(4, c // cg, cg)              # theta is tiled: channel ch -> ch % cg
         th = th.sum(1) if c != cg else th[:, 0]
         g_wpos = th[1:4].t().contiguous().view(sh[3])
@@ -928,8 +947,8 @@ class _ElkCoreTrain(torch.autograd.Function):
 def elk_core_train(feats, coords, index, w_pre, pre_ln_w, pre_ln_b, w_pos, alpha, ln_w, ln_b, baseop,
                    cg, r, coord_div=1.0, eps=1e-6):
     """Differentiable R_core for training.  C % 16 == 0 (<= 128): everything hand-written
-    (_ElkCoreTrain).  Other multiples of 4: pre_mix Linear + the two LayerNorms through torch autograd,
-    the middle through _ElkMid."""
+    (_ElkCoreTrain; fp32, or fp16 / bf16 rows with fp32 parameters).  Other multiples of 4: pre_mix Linear + the
+    two LayerNorms through torch autograd, the middle through _ElkMid."""
     c = feats.shape[1]
     if c % 16 == 0 and c <= 128:
         return _ElkCoreTrain.apply(feats, w_pre, pre_ln_w, pre_ln_b, w_pos, alpha, ln_w, ln_b, index,
@@ -1135,10 +1154,18 @@ class Conv3d(nn.Module):
         return km
 
     def forward(self, x: SparseTensor) -> SparseTensor:
-        feats = x.F
+        if x.F.is_cuda and torch.is_autocast_enabled("cuda"):
+            # the reference's custom_fwd(cast_inputs=torch.half) (nn/functional/conv.py:19): rows, kernel and bias in fp16,
+            # under a bf16 region too, autocast off inside.  The kernel stays the fp32 parameter here: the AMP kernels round
+            # it to fp16 themselves (_amp_weights), and its gradient comes back in fp32 from the fp32 weight-gradient kernels
+            with torch.autocast("cuda", enabled=False):
+                return self._forward(x, x.F.half(), self.bias.half() if self.bias is not None else None, half=True)
+        return self._forward(x, x.F, self.bias)
+
+    def _forward(self, x: SparseTensor, feats: torch.Tensor, bias: Optional[torch.Tensor], half: bool = False) -> SparseTensor:
         if self.stride[0] == 1:
             if self.kernel_volume == 1:
-                out = feats.matmul(self.kernel)
+                out = feats.matmul(self.kernel.half() if half else self.kernel)
             else:
                 nbr, order = self._neighbor_table(x)
                 out = _SubmConv.apply(feats, self.kernel, nbr, order)
@@ -1152,8 +1179,8 @@ class Conv3d(nn.Module):
             km = x.kmaps[(stride, self.kernel_size, self.stride, self.dilation)]   # the matching down-conv's map
             out = _GatherConv.apply(feats, self.kernel, km.nbr_up, km.nbr_down)
             coords = x.cmaps[stride]
-        if self.bias is not None:
-            out = out + self.bias
+        if bias is not None:
+            out = out + bias
         y = SparseTensor(out, coords, stride)
         y.cmaps, y.kmaps = x.cmaps, x.kmaps
         y.cmaps.setdefault(y.stride, y.coords)
@@ -1742,19 +1769,27 @@ def subm_conv_ln_add_relu(feats: torch.Tensor, kernel: torch.Tensor, nbr: torch.
 
 
 class _Tail(torch.autograd.Function):
-    """relu(addend + LayerNorm(x)) with a hand-written backward (link_ln_add_relu_forward/backward)."""
+    """relu(addend + LayerNorm(x)) with a hand-written backward (link_ln_add_relu_forward/backward).
+    fp16 / bf16 x with an fp32 addend (autocast training): x is read as it is (link_ln_add_relu_*_io), the output
+    is fp32 as autocast's LayerNorm gives it, g_x comes back in x's type."""
 
     @staticmethod
     def forward(ctx, x, addend, ln_w, ln_b, eps):
         n, c = x.shape
-        x = x.detach().contiguous().float()
+        io = _IO_DTYPES.get(x.dtype, L.IO_F32) if addend.dtype == torch.float32 else L.IO_F32
+        x = x.detach().contiguous()
+        x = x if io != L.IO_F32 else x.float()
         a = addend.detach().contiguous().float()
         w, b = ln_w.detach().contiguous().float(), ln_b.detach().contiguous().float()
-        y = torch.empty_like(x)
-        L.check(L.lib().link_ln_add_relu_forward(x.data_ptr(), a.data_ptr(), w.data_ptr(), b.data_ptr(), n, c,
-                                                 float(eps), y.data_ptr(), _st()), "link_ln_add_relu_forward")
+        y = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        if io == L.IO_F32:
+            L.check(L.lib().link_ln_add_relu_forward(x.data_ptr(), a.data_ptr(), w.data_ptr(), b.data_ptr(), n, c,
+                                                     float(eps), y.data_ptr(), _st()), "link_ln_add_relu_forward")
+        else:
+            L.check(L.lib().link_ln_add_relu_forward_io(x.data_ptr(), io, a.data_ptr(), w.data_ptr(), b.data_ptr(), n, c,
+                                                        float(eps), y.data_ptr(), _st()), "link_ln_add_relu_forward_io")
         ctx.save_for_backward(x, y, w)
-        ctx.eps = float(eps)
+        ctx.eps, ctx.io = float(eps), io
         return y
 
     @staticmethod
@@ -1764,11 +1799,16 @@ class _Tail(torch.autograd.Function):
         lib = L.lib()
         rows = int(lib.link_elk_mid_partial_rows())
         g = g.contiguous().float()
-        g_add, g_x = torch.empty_like(x), torch.empty_like(x)
+        g_add, g_x = torch.empty_like(y), torch.empty_like(x)
         part = torch.empty(rows * 2 * c + 2 * c, dtype=torch.float32, device=x.device)
-        L.check(lib.link_ln_add_relu_backward(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), n, c, ctx.eps,
-                                              g_add.data_ptr(), g_x.data_ptr(), part.data_ptr(), _st()),
-                "link_ln_add_relu_backward")
+        if ctx.io == L.IO_F32:
+            L.check(lib.link_ln_add_relu_backward(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), n, c, ctx.eps,
+                                                  g_add.data_ptr(), g_x.data_ptr(), part.data_ptr(), _st()),
+                    "link_ln_add_relu_backward")
+        else:
+            L.check(lib.link_ln_add_relu_backward_io(g.data_ptr(), y.data_ptr(), x.data_ptr(), ctx.io, w.data_ptr(), n, c,
+                                                     ctx.eps, g_add.data_ptr(), g_x.data_ptr(), part.data_ptr(), _st()),
+                    "link_ln_add_relu_backward_io")
         tot = part[rows * 2 * c:]
         L.check(lib.link_sum_partials(part.data_ptr(), 2 * c, None, 0, None, 0, rows, tot.data_ptr(), _st()),
                 "link_sum_partials")
@@ -1842,10 +1882,11 @@ class _GatherConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         feats, kernel, table, table_back = ctx.saved_tensors
+        g16 = g.contiguous().half() if feats.dtype == torch.float16 else None     # fp16 rows: see _SubmConv.backward
         g = g.contiguous().float()
         g_feats = g_kernel = None
         if ctx.needs_input_grad[0]:
-            g_feats = subm_conv(g, kernel.detach().transpose(1, 2).contiguous(), table_back, None)
+            g_feats = subm_conv(g16 if g16 is not None else g, kernel.detach().transpose(1, 2).contiguous(), table_back, None)
         if ctx.needs_input_grad[1]:
             g_kernel = _conv_weight_grad(feats, g, table, kernel.shape)
         return g_feats, g_kernel, None, None
@@ -1866,7 +1907,10 @@ def _flipped_weights(kernel: torch.Tensor) -> torch.Tensor:
 class _SubmConv(torch.autograd.Function):
     """Differentiable stride-1 submanifold convolution on the HIP kernel.  Input gradient: the same
     kernel on grad_out with w'[k] = w[K-1-k]^T (odd kernel, same coordinates: nbr[v,k] = u  <=>
-    nbr[u,K-1-k] = v).  Weight gradient: per offset gather + one batched library GEMM."""
+    nbr[u,K-1-k] = v).  Weight gradient: per offset gather + one batched library GEMM.
+    fp16 rows (autocast: Conv3d.forward): the input gradient runs on the same AMP forward kernels with fp16 grad_out
+    rows and the flipped weights rounded to fp16, and comes back fp16 (the reference's custom_bwd); the weight
+    gradient stays on the fp32 kernels over the widened rows and comes back fp32 (_GatherConv likewise)."""
 
     @staticmethod
     def forward(ctx, feats, kernel, nbr, order=None):
@@ -1877,10 +1921,11 @@ class _SubmConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         feats, kernel, nbr = ctx.saved_tensors
+        g16 = g.contiguous().half() if feats.dtype == torch.float16 else None
         g = g.contiguous().float()
         g_feats = g_kernel = None
         if ctx.needs_input_grad[0]:
-            g_feats = subm_conv(g, _flipped_weights(kernel), nbr, ctx.order)
+            g_feats = subm_conv(g16 if g16 is not None else g, _flipped_weights(kernel), nbr, ctx.order)
         if ctx.needs_input_grad[1]:
             g_kernel = _conv_weight_grad(feats, g, nbr, kernel.shape)
         return g_feats, g_kernel, None, None
@@ -2338,8 +2383,15 @@ class _ELKBase(nn.Module):
         if needs_grad:
             if st.F.shape[1] % 4 == 0 and r <= 3 and st.F.dtype == torch.float32:
                 return elk_core_train(*args)
+            if self._amp_rows(st.F) and st.F.shape[1] % 16 == 0 and st.F.shape[1] <= 128 and r <= 3:
+                return elk_core_train(*args)     # autocast training: 16-bit rows on the hand-written kernels
             return elk_core_autograd(*args)      # op-by-op composition: any width / r
         return elk_core_fused(*args)
+
+    def _amp_rows(self, f: torch.Tensor) -> bool:
+        """fp16 / bf16 rows into a module whose parameters are fp32 (what torch.autocast produces; a model cast to half as
+        a whole is not meant): the 16-bit training paths of _core / _finish."""
+        return f.dtype in (torch.float16, torch.bfloat16) and f.is_cuda and all(p.dtype == torch.float32 for p in self.parameters())
 
     def _finish(self, st: SparseTensor, core_fn, core_args=None):
         """st.F = relu(core + norm_local(local_mix(st).F))  (linkunet.py:125,183 / ts_elk.py:146,228).
@@ -2359,8 +2411,9 @@ class _ELKBase(nn.Module):
             local = self.local_mix(st)
             new = core_fn()
             nl = self.norm_local
-            if (needs_grad and not hooked and st.F.dtype == torch.float32 and new.shape[1] % 4 == 0
-                    and new.shape[1] <= 256 and new.is_cuda):
+            if (needs_grad and not hooked and new.shape[1] % 4 == 0 and new.shape[1] <= 256 and new.is_cuda
+                    and (st.F.dtype == torch.float32
+                         or (new.dtype == torch.float32 and self._amp_rows(st.F)))):
                 st.F = _Tail.apply(local.F, new, nl.weight, nl.bias, nl.eps)     # fused tail, fused backward
             else:
                 st.F = self.activate(new + nl(local.F))

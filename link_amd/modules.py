@@ -22,7 +22,9 @@ def fapply(input: SparseTensor, fn: Callable[..., torch.Tensor], *args, **kwargs
 class _BatchNormTrain(torch.autograd.Function):
     """Training-mode BatchNorm over feature rows with the statistics on the HIP column-reduction kernels
     (include/link_amd.h section F): y = (x - mean) * scale + shift with batch statistics, running statistics updated in
-    place; backward: grad_x = a * g + bq * (x - mean) + cq per channel, grad_weight = sum g * xhat, grad_bias = sum g."""
+    place; backward: grad_x = a * g + bq * (x - mean) + cq per channel, grad_weight = sum g * xhat, grad_bias = sum g.
+    fp16 / bf16 rows (autocast training, fp32 weight): the *_io entries read x / g and write y / grad_x in the row type, as
+    torch's batch_norm returns them; statistics and running statistics stay fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu=False):
@@ -32,23 +34,33 @@ class _BatchNormTrain(torch.autograd.Function):
         from . import _lib as L
         n, c = x.shape
         x = x.contiguous()
+        io = {torch.float16: L.IO_F16, torch.bfloat16: L.IO_BF16}.get(x.dtype, L.IO_F32)
         lib, st = L.lib(), L.current_stream_handle()
         partial = torch.empty(int(lib.link_bn_partial_workgroups(n, c)) * 2 * c, dtype=torch.float64, device=x.device)
         vec = torch.empty((4, c), dtype=torch.float32, device=x.device)          # mean | invstd | scale | shift
         w = weight.detach().contiguous() if weight is not None else None
         b = bias.detach().contiguous() if bias is not None else None
-        L.check(lib.link_bn_forward_stats(x.data_ptr(), n, c, float(eps), float(momentum), partial.data_ptr(), vec[0].data_ptr(),
-                                          vec[1].data_ptr(), running_mean.data_ptr() if running_mean is not None else None,
-                                          running_var.data_ptr() if running_var is not None else None,
-                                          w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None,
-                                          vec[2].data_ptr(), vec[3].data_ptr(), st), "link_bn_forward_stats")
+        stats = (n, c, float(eps), float(momentum), partial.data_ptr(), vec[0].data_ptr(),
+                 vec[1].data_ptr(), running_mean.data_ptr() if running_mean is not None else None,
+                 running_var.data_ptr() if running_var is not None else None,
+                 w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None,
+                 vec[2].data_ptr(), vec[3].data_ptr(), st)
+        if io == L.IO_F32:
+            L.check(lib.link_bn_forward_stats(x.data_ptr(), *stats), "link_bn_forward_stats")
+        else:
+            L.check(lib.link_bn_forward_stats_io(x.data_ptr(), io, *stats), "link_bn_forward_stats_io")
         ctx.save_for_backward(x, vec, *((w,) if w is not None else ()))
         ctx.partial = partial
         ctx.has_wb = (weight is not None, bias is not None)
         ctx.relu = bool(relu)
+        ctx.io = io
         y = torch.empty_like(x)                                   # y = (x - mean) * scale + shift, centred first: no cancellation
-        L.check(lib.link_bn_apply_forward(x.data_ptr(), vec[0].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), n, c,
-                                          1 if relu else 0, y.data_ptr(), st), "link_bn_apply_forward")
+        if io == L.IO_F32:
+            L.check(lib.link_bn_apply_forward(x.data_ptr(), vec[0].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), n, c,
+                                              1 if relu else 0, y.data_ptr(), st), "link_bn_apply_forward")
+        else:
+            L.check(lib.link_bn_apply_forward_io(x.data_ptr(), io, vec[0].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), n, c,
+                                                 1 if relu else 0, y.data_ptr(), st), "link_bn_apply_forward_io")
         return y
 
     @staticmethod
@@ -60,6 +72,26 @@ class _BatchNormTrain(torch.autograd.Function):
         g = g.contiguous()
         lib, st = L.lib(), L.current_stream_handle()
         out = torch.empty((5, c), dtype=torch.float32, device=x.device)           # sum_g | sum_gx | a | bq | cq
+        io = ctx.io
+        if io != L.IO_F32:                                    # 16-bit rows: g in the row type (y's), read as it is
+            g = g.to(x.dtype)
+            wp = w.data_ptr() if w is not None else None
+            if ctx.relu:
+                L.check(lib.link_bn_backward_reduce_relu_io(g.data_ptr(), x.data_ptr(), io, vec[0].data_ptr(), vec[1].data_ptr(),
+                                                            vec[2].data_ptr(), vec[3].data_ptr(), n, c, ctx.partial.data_ptr(),
+                                                            out[0].data_ptr(), out[1].data_ptr(), wp, out[2].data_ptr(), st),
+                        "link_bn_backward_reduce_relu_io")
+            else:
+                L.check(lib.link_bn_backward_reduce_io(g.data_ptr(), x.data_ptr(), io, vec[0].data_ptr(), vec[1].data_ptr(), n, c,
+                                                       ctx.partial.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), wp,
+                                                       out[2].data_ptr(), st), "link_bn_backward_reduce_io")
+            gx = None
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty_like(x)
+                L.check(lib.link_bn_apply_backward_io(g.data_ptr(), x.data_ptr(), io, vec[0].data_ptr(), out[2].data_ptr(),
+                                                      vec[2].data_ptr() if ctx.relu else None, vec[3].data_ptr() if ctx.relu else None,
+                                                      n, c, gx.data_ptr(), st), "link_bn_apply_backward_io")
+            return gx, (out[1] if ctx.has_wb[0] else None), (out[0] if ctx.has_wb[1] else None), None, None, None, None, None
         g = g.float()
         if ctx.relu:                                          # g masked by y > 0 inside both passes (y recomputed from x)
             L.check(lib.link_bn_backward_reduce_relu(g.data_ptr(), x.data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
@@ -82,12 +114,18 @@ class _BatchNormTrain(torch.autograd.Function):
 
 class BatchNorm(nn.BatchNorm1d):
     """torchsparse/nn/modules/norm.py:10-13.  Training mode on GPU rows runs the batch statistics through the HIP
-    column reductions (_BatchNormTrain); everything else (eval, CPU, half rows, momentum=None) is nn.BatchNorm1d."""
+    column reductions (_BatchNormTrain): fp32 rows, and fp16 / bf16 rows with grad enabled into fp32 parameters (autocast
+    training).  Everything else (eval, CPU, a module cast to half, momentum=None) is nn.BatchNorm1d."""
 
     hip_stats = True
 
     def _hip_train_ok(self, x: torch.Tensor) -> bool:
-        return (self.hip_stats and self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 1
+        if x.dtype in (torch.float16, torch.bfloat16):
+            rows_ok = torch.is_grad_enabled() and all(
+                t is None or t.dtype == torch.float32 for t in (self.bias, self.running_mean, self.running_var))
+        else:
+            rows_ok = x.dtype == torch.float32
+        return (self.hip_stats and self.training and x.is_cuda and rows_ok and x.dim() == 2 and x.shape[0] > 1
                 and x.shape[1] % 4 == 0 and 4 <= x.shape[1] <= 1024 and self.momentum is not None
                 and (self.weight is None or self.weight.dtype == torch.float32))
 
