@@ -13,6 +13,7 @@
 // IO (row_io.h): the type of the [N, C] rows -- x, g, the normalised output and the input gradient -- at the kernel boundary;
 // statistics, coefficients and running statistics stay fp32 / f64 (the *_io entries: autocast training, 16-bit rows).
 #include "common.h"
+#include "dispatch.h"
 #include "row_io.h"
 
 using namespace link;
@@ -285,49 +286,40 @@ extern "C" int link_bn_apply_backward(const float *g, const float *x, const floa
 
 // 16-bit rows (io_dtype = LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16 for x, g, y, gx): the same kernels with the rows widened on
 // load and rounded (RNE) on store -- autocast training, where a BatchNorm sees the half rows of the convolution before it
-#define LINK_BN_IO(CALL)                                               \
-  switch (io_dtype) {                                                  \
-    case LINK_IO_F32: return CALL(LINK_IO_F32);                        \
-    case LINK_IO_F16: return CALL(LINK_IO_F16);                        \
-    case LINK_IO_BF16: return CALL(LINK_IO_BF16);                      \
-    default: return LINK_ERR_ARG;                                      \
-  }
-
 extern "C" int link_bn_forward_stats_io(const void *x, int32_t io_dtype, int64_t n, int32_t c, float eps, float momentum,
                                         double *partial, float *mean, float *invstd, float *running_mean, float *running_var,
                                         const float *weight, const float *bias, float *scale, float *shift, void *stream) {
-#define LINK_C(IO) bn_forward_stats<IO>(x, n, c, eps, momentum, partial, mean, invstd, running_mean, running_var, weight, bias, scale, shift, stream)
-  LINK_BN_IO(LINK_C)
-#undef LINK_C
+  int rc = LINK_ERR_ARG;
+  dispatch_row_io(io_dtype, [&](auto io) { rc = bn_forward_stats<decltype(io)::value>(x, n, c, eps, momentum, partial, mean, invstd, running_mean, running_var, weight, bias, scale, shift, stream); });
+  return rc;
 }
 
 extern "C" int link_bn_apply_forward_io(const void *x, int32_t io_dtype, const float *mean, const float *scale, const float *shift,
                                         int64_t n, int32_t c, int32_t relu, void *y, void *stream) {
-#define LINK_C(IO) bn_apply_forward<IO>(x, mean, scale, shift, n, c, relu, y, stream)
-  LINK_BN_IO(LINK_C)
-#undef LINK_C
+  int rc = LINK_ERR_ARG;
+  dispatch_row_io(io_dtype, [&](auto io) { rc = bn_apply_forward<decltype(io)::value>(x, mean, scale, shift, n, c, relu, y, stream); });
+  return rc;
 }
 
 extern "C" int link_bn_backward_reduce_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd,
                                           int64_t n, int32_t c, double *partial, float *sum_g, float *sum_gx, const float *weight,
                                           float *coef, void *stream) {
-#define LINK_C(IO) bn_backward_reduce<IO>(g, x, mean, invstd, nullptr, nullptr, n, c, partial, sum_g, sum_gx, weight, coef, false, stream)
-  LINK_BN_IO(LINK_C)
-#undef LINK_C
+  int rc = LINK_ERR_ARG;
+  dispatch_row_io(io_dtype, [&](auto io) { rc = bn_backward_reduce<decltype(io)::value>(g, x, mean, invstd, nullptr, nullptr, n, c, partial, sum_g, sum_gx, weight, coef, false, stream); });
+  return rc;
 }
 
 extern "C" int link_bn_backward_reduce_relu_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *invstd,
                                                const float *scale, const float *shift, int64_t n, int32_t c, double *partial,
                                                float *sum_g, float *sum_gx, const float *weight, float *coef, void *stream) {
-#define LINK_C(IO) bn_backward_reduce<IO>(g, x, mean, invstd, scale, shift, n, c, partial, sum_g, sum_gx, weight, coef, true, stream)
-  LINK_BN_IO(LINK_C)
-#undef LINK_C
+  int rc = LINK_ERR_ARG;
+  dispatch_row_io(io_dtype, [&](auto io) { rc = bn_backward_reduce<decltype(io)::value>(g, x, mean, invstd, scale, shift, n, c, partial, sum_g, sum_gx, weight, coef, true, stream); });
+  return rc;
 }
 
 extern "C" int link_bn_apply_backward_io(const void *g, const void *x, int32_t io_dtype, const float *mean, const float *coef,
                                          const float *scale, const float *shift, int64_t n, int32_t c, void *gx, void *stream) {
-#define LINK_C(IO) bn_apply_backward<IO>(g, x, mean, coef, scale, shift, n, c, gx, stream)
-  LINK_BN_IO(LINK_C)
-#undef LINK_C
+  int rc = LINK_ERR_ARG;
+  dispatch_row_io(io_dtype, [&](auto io) { rc = bn_apply_backward<decltype(io)::value>(g, x, mean, coef, scale, shift, n, c, gx, stream); });
+  return rc;
 }
-#undef LINK_BN_IO

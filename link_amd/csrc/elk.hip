@@ -1,6 +1,8 @@
 // link_amd/csrc/elk.hip -- section C of include/link_amd.h: the fused R_core of ELKBlock.forward
 // (segmentation/core/models/semantic_kitti/linkunet.py:124-185; detection/det3d/models/utils/
-// ts_elk.py:144-230) for gfx950.
+// ts_elk.py:144-230) for gfx950, general layout: the op-level forward entries, the one-call
+// link_elk_core_forward, and aux_to_voxel on the block-gather kernel.  The training form
+// (elk_train.hip) runs three of these kernels through elk_host.h; template axes: dispatch.h.
 //
 //   k_premix_ln_tlp      fin = LayerNorm(F @ Wpre^T): the only GEMM-shaped step -> f32 MFMA
 //                        (v_mfma_f32_16x16x4_f32, exact f32), W staged once per workgroup in LDS
@@ -22,13 +24,21 @@
 // validity selects) and then the m_cap+1 per-block counts (fp32) at S + (m_cap+1)*P*C.
 #include <limits.h>
 
+#include "dispatch.h"
 #include "elk_common.h"
+#include "elk_host.h"
 #include "row_io.h"
 
 using namespace link;
 
-static int g_premix_wgs_fwd();
-static bool g_wt_fwd();
+// launch geometry (fixed: chosen from the sweeps recorded in DESIGN.md 5a; nothing here is mutable process state -- the
+// alternative kernel paths are selected per call through link_elk_desc_t::flags)
+static constexpr int g_modsum_wgs = 1024;   // flat 512..2048 in the sweep, smaller grids co-run better
+static constexpr int g_gather_wgs = 1024;   // 4 waves/SIMD resident at ~100 VGPRs -> one resident round
+static constexpr int g_premix_wgs = 1024;
+static constexpr int g_coop_threshold = 4;  // mean voxels/block above which a wave's groups cooperate per block
+static constexpr int g_bgather_wgs = 512;
+static constexpr int g_wt = 15;             // write-through (sc1) output stores in all four streaming kernels
 
 // ---------------------------------------------------------------------------------------------
 // pre_mix + LayerNorm (MFMA path, C % 16 == 0, C <= 128)
@@ -116,7 +126,7 @@ static int launch_premix_tlp(const void *feats, const float *w_pre, const float 
   size_t lds = (size_t)C * (C + 4) * sizeof(float);
   int64_t tiles = (n + 15) / 16;
   int64_t wgs = (tiles + 3) / 4;
-  if (wgs > g_premix_wgs_fwd()) wgs = g_premix_wgs_fwd();
+  if (wgs > g_premix_wgs) wgs = g_premix_wgs;
   if (lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in once per kernel (160 KB per CU on gfx950)
     // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
     // device reset would never pass again
@@ -124,8 +134,19 @@ static int launch_premix_tlp(const void *feats, const float *w_pre, const float 
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
   hipLaunchKernelGGL((k_premix_ln_tlp<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, ln_b, n,
-                     eps, fin, g_wt_fwd() && wt_ok(n, C));
+                     eps, fin, (g_wt & 1) != 0 && wt_ok(n, C));
   return check_launch("link_premix_ln");
+}
+
+// the MFMA kernel for the row widths and row types it is built for (the one place both are chosen); false: c is none of them
+static bool premix_mfma(const void *feats, int io_dtype, const float *w_pre, const float *ln_w, const float *ln_b, int64_t n,
+                        int c, float eps, float *fin, hipStream_t st, int *rc) {
+  return dispatch_width(c, [&](auto w) {
+    constexpr int C = decltype(w)::value;
+    return dispatch_row_io(io_dtype, [&](auto io) {
+      *rc = launch_premix_tlp<C, decltype(io)::value>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
+    });
+  });
 }
 
 // generic fallback (any C <= 256): one wave per voxel, lanes = output channels, W read through L1/L2
@@ -177,26 +198,28 @@ extern "C" int link_premix_ln(const float *feats, const float *w_pre, const floa
   if (n == 0) return LINK_OK;
   if (!feats || !w_pre || !ln_w || !ln_b || !fin) return LINK_ERR_ARG;
   hipStream_t st = S(stream);
-  switch (c) {
-    case 16: return launch_premix_tlp<16>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 32: return launch_premix_tlp<32>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 48: return launch_premix_tlp<48>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 64: return launch_premix_tlp<64>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 80: return launch_premix_tlp<80>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 96: return launch_premix_tlp<96>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 112: return launch_premix_tlp<112>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 128: return launch_premix_tlp<128>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    default: break;
-  }
+  int rc = LINK_OK;
+  if (premix_mfma(feats, LINK_IO_F32, w_pre, ln_w, ln_b, n, c, eps, fin, st, &rc)) return rc;
   dim3 grid(blocks_for(n * 64, 256)), block(256);
-  int cpl = (c + 63) / 64;
-  if (cpl == 1) hipLaunchKernelGGL(k_premix_ln_generic<1>, grid, block, 0, st, feats, w_pre, ln_w, ln_b, n, (int)c, eps, fin);
-  else if (cpl == 2) hipLaunchKernelGGL(k_premix_ln_generic<2>, grid, block, 0, st, feats, w_pre, ln_w, ln_b, n, (int)c, eps, fin);
-  else if (cpl == 3) hipLaunchKernelGGL(k_premix_ln_generic<3>, grid, block, 0, st, feats, w_pre, ln_w, ln_b, n, (int)c, eps, fin);
-  else hipLaunchKernelGGL(k_premix_ln_generic<4>, grid, block, 0, st, feats, w_pre, ln_w, ln_b, n, (int)c, eps, fin);
+  if (!dispatch_cpl(c, [&](auto cpl) {
+        hipLaunchKernelGGL(k_premix_ln_generic<decltype(cpl)::value>, grid, block, 0, st, feats, w_pre, ln_w, ln_b, n, (int)c, eps, fin);
+      }))
+    return LINK_ERR_ARG;
   return check_launch("link_premix_ln");
 }
 
+// 16-bit feats rows (autocast training; row_io.h): widened on load, fin stays fp32
+extern "C" int link_premix_ln_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w, const float *ln_b,
+                                 int64_t n, int32_t c, float eps, float *fin, void *stream) {
+  if (!row_io_ok(io_dtype)) return LINK_ERR_ARG;
+  if (io_dtype == LINK_IO_F32) return link_premix_ln(reinterpret_cast<const float *>(feats), w_pre, ln_w, ln_b, n, c, eps, fin, stream);
+  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;     // 16-bit rows: the MFMA widths only
+  if (n == 0) return LINK_OK;
+  if (!feats || !w_pre || !ln_w || !ln_b || !fin) return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  premix_mfma(feats, io_dtype, w_pre, ln_w, ln_b, n, c, eps, fin, S(stream), &rc);
+  return rc;
+}
 
 // Work partition shared by the two block kernels: the sorted block range [0,M) is cut into 8
 // contiguous slabs, one per XCD (workgroup w runs on XCD w % 8 -- observed dispatch, used for L2
@@ -315,62 +338,11 @@ __global__ void __launch_bounds__(256) k_modulate_sum(const float *__restrict__ 
   }
 }
 
-// launch geometry (fixed: chosen from the sweeps recorded in DESIGN.md 5a; nothing here is mutable process state -- the
-// alternative kernel paths are selected per call through link_elk_desc_t::flags)
-static constexpr int g_modsum_wgs = 1024;   // flat 512..2048 in the sweep, smaller grids co-run better
-static constexpr int g_gather_wgs = 1024;   // 4 waves/SIMD resident at ~100 VGPRs -> one resident round
-static constexpr int g_premix_wgs = 1024;
-static constexpr int g_coop_threshold = 4;  // mean voxels/block above which a wave's groups cooperate per block
-static constexpr int g_bgather_wgs = 512;
-static constexpr int g_wt = 15;             // write-through (sc1) output stores in all four streaming kernels
-
-template <int CPL>
-static void launch_modsum(int op, hipStream_t st, const float *fin, const int4 *vox, const float *w_pos,
-                          const float *alpha, const int32_t *blk_start, const int32_t *hdr, int c, int cg,
-                          float div, float *S, int64_t m_cap) {
-  dim3 grid(g_modsum_wgs), block(256);
-  if (op == LINK_OP_COS)
-    hipLaunchKernelGGL((k_modulate_sum<CPL, LINK_OP_COS>), grid, block, 0, st, fin, vox, w_pos, alpha, blk_start, hdr, c, cg, div, S, m_cap);
-  else if (op == LINK_OP_SIN)
-    hipLaunchKernelGGL((k_modulate_sum<CPL, LINK_OP_SIN>), grid, block, 0, st, fin, vox, w_pos, alpha, blk_start, hdr, c, cg, div, S, m_cap);
-  else
-    hipLaunchKernelGGL((k_modulate_sum<CPL, LINK_OP_COSX>), grid, block, 0, st, fin, vox, w_pos, alpha, blk_start, hdr, c, cg, div, S, m_cap);
-}
-
-static bool modsum_group_path(const link_elk_desc_t *d, hipStream_t st, const float *fin, const int4 *vox,
-                              const float *w_pos, const float *alpha, const int32_t *blk_start,
-                              const int32_t *hdr, float *S_, int64_t m_cap, int op = -1,
-                              const float *row_den = nullptr);
-static bool gather_group_path(const link_elk_desc_t *d, hipStream_t st, const float *S_, const float *fin,
-                              const int4 *vox, const float *w_pos, const float *alpha, const float *ln_w,
-                              const float *ln_b, const int32_t *blk_start, const int4 *blk_coords,
-                              const int32_t *cell_blk, const link_grid_t &g, const int32_t *hdr, float *out,
-                              int64_t m_cap);
-static int check_desc(const link_elk_desc_t *d) {
+int link::check_desc(const link_elk_desc_t *d) {
   if (!d) return LINK_ERR_ARG;
   if (d->op < 0 || d->op > 2 || d->c <= 0 || d->c > 256 || d->cg <= 0 || d->cg > d->c) return LINK_ERR_ARG;
   if (d->r <= 0 || d->r > 7 || d->coord_div == 0.f) return LINK_ERR_ARG;
   return LINK_OK;
-}
-
-extern "C" int link_modulate_block_sum(const float *fin, const int32_t *vox_sorted, const float *w_pos,
-                                       const float *alpha, const int32_t *blk_start, const int32_t *hdr,
-                                       const link_elk_desc_t *desc, int64_t n, int64_t m_cap, float *S_,
-                                       void *stream) {
-  if (check_desc(desc) != LINK_OK || n < 0 || m_cap < 0) return LINK_ERR_ARG;
-  if (n == 0 || m_cap == 0) return LINK_OK;
-  if (!fin || !vox_sorted || !w_pos || !blk_start || !hdr || !S_) return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  int cpl = (desc->c + 63) / 64;
-  hipStream_t st = S(stream);
-  if (modsum_group_path(desc, st, fin, v4, w_pos, alpha, blk_start, hdr, S_, m_cap)) return check_launch("link_modulate_block_sum");
-  switch (cpl) {
-    case 1: launch_modsum<1>(desc->op, st, fin, v4, w_pos, alpha, blk_start, hdr, desc->c, desc->cg, desc->coord_div, S_, m_cap); break;
-    case 2: launch_modsum<2>(desc->op, st, fin, v4, w_pos, alpha, blk_start, hdr, desc->c, desc->cg, desc->coord_div, S_, m_cap); break;
-    case 3: launch_modsum<3>(desc->op, st, fin, v4, w_pos, alpha, blk_start, hdr, desc->c, desc->cg, desc->coord_div, S_, m_cap); break;
-    default: launch_modsum<4>(desc->op, st, fin, v4, w_pos, alpha, blk_start, hdr, desc->c, desc->cg, desc->coord_div, S_, m_cap); break;
-  }
-  return check_launch("link_modulate_block_sum");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -581,68 +553,6 @@ __global__ void __launch_bounds__(256) k_gather_demod_ln(
   }
 }
 
-template <int CPL, int OP>
-static void launch_gdl_r(int r, hipStream_t st, int64_t m_cap, const float *S_, const float *fin, const int4 *vox,
-                         const float *w_pos, const float *alpha, const float *ln_w, const float *ln_b,
-                         const int32_t *blk_start, const int4 *blk_coords, const int32_t *cell_blk,
-                         const link_grid_t &g, const int32_t *hdr, const link_elk_desc_t &d, float *out) {
-  dim3 grid(g_gather_wgs), block(256);
-#define LINK_GDL(RR)                                                                                   \
-  hipLaunchKernelGGL((k_gather_demod_ln<CPL, OP, RR>), grid, block, 0, st, S_, fin, vox, w_pos, alpha, \
-                     ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d.c, d.cg, d.coord_div, d.eps, out, m_cap)
-  switch (r) {
-    case 1: LINK_GDL(1); break;
-    case 2: LINK_GDL(2); break;
-    case 3: LINK_GDL(3); break;
-    case 4: LINK_GDL(4); break;
-    default: LINK_GDL(5); break;
-  }
-#undef LINK_GDL
-}
-
-template <int CPL>
-static void launch_gdl(int op, int r, hipStream_t st, int64_t m_cap, const float *S_, const float *fin, const int4 *vox,
-                       const float *w_pos, const float *alpha, const float *ln_w, const float *ln_b,
-                       const int32_t *blk_start, const int4 *blk_coords, const int32_t *cell_blk,
-                       const link_grid_t &g, const int32_t *hdr, const link_elk_desc_t &d, float *out) {
-  if (op == LINK_OP_COS)
-    launch_gdl_r<CPL, LINK_OP_COS>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
-  else if (op == LINK_OP_SIN)
-    launch_gdl_r<CPL, LINK_OP_SIN>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
-  else
-    launch_gdl_r<CPL, LINK_OP_COSX>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
-}
-
-extern "C" int link_gather_demod_ln(const float *S_, const float *fin, const int32_t *vox_sorted,
-                                    const float *w_pos, const float *alpha, const float *ln_w,
-                                    const float *ln_b, const int32_t *blk_start,
-                                    const int32_t *blk_coords, const int32_t *cell_blk,
-                                    const link_grid_t *grid, const int32_t *hdr,
-                                    const link_elk_desc_t *desc, int64_t n, int64_t m_cap, float *out,
-                                    void *stream) {
-  if (check_desc(desc) != LINK_OK || !grid || n < 0 || m_cap < 0 || desc->r > 5) return LINK_ERR_ARG;
-  if (n == 0 || m_cap == 0) return LINK_OK;
-  if (!S_ || !vox_sorted || !w_pos || !ln_w || !ln_b || !blk_start || !blk_coords || !cell_blk || !hdr || !out)
-    return LINK_ERR_ARG;
-  if (desc->op == LINK_OP_COSX && !fin) return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  const int4 *b4 = reinterpret_cast<const int4 *>(blk_coords);
-  hipStream_t st = S(stream);
-  int cpl = (desc->c + 63) / 64;
-  if (gather_group_path(desc, st, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, out, m_cap))
-    return check_launch("link_gather_demod_ln");
-  switch (cpl) {
-    case 1: launch_gdl<1>(desc->op, desc->r, st, m_cap, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, *desc, out); break;
-    case 2: launch_gdl<2>(desc->op, desc->r, st, m_cap, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, *desc, out); break;
-    case 3: launch_gdl<3>(desc->op, desc->r, st, m_cap, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, *desc, out); break;
-    default: launch_gdl<4>(desc->op, desc->r, st, m_cap, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, *desc, out); break;
-  }
-  return check_launch("link_gather_demod_ln");
-}
-
-static int g_premix_wgs_fwd() { return g_premix_wgs; }
-static bool g_wt_fwd() { return (g_wt & 1) != 0; }
-
 // =============================================================================================
 // Sub-wave ("group") kernels: the fast path for C % 4 == 0.
 //
@@ -724,7 +634,6 @@ __device__ __forceinline__ void modulate_sum_per_group(const float *__restrict__
   auto ld_rec = [&](int q) { return vox_sorted[(q <= p_last) ? q : p_last]; };
   auto ld_row = [&](int i) { return *reinterpret_cast<const float4 *>(&fin[(int64_t)i * c + cofs]); };
   auto flush = [&]() {                            // block finished: one row write, no atomics
-    float *row = S + (int64_t)b * rs;
     const float k = row_den ? 1.0f / row_den[b] : 1.0f;    // backward: rows pre-divided by the forward's denominator
     if (act) {
       store_out(S, (int64_t)b * rs + ch0, make_float4(a0[0] * k, a0[1] * k, a0[2] * k, a0[3] * k), wt);
@@ -779,7 +688,6 @@ __device__ __forceinline__ void modulate_sum_per_group(const float *__restrict__
     rcA = rnA; rcB = rnB; rnA = r2A; rnB = r2B; fcA = fnA; fcB = fnB;
   }
   {                                               // last block of the chunk
-    float *row = S + (int64_t)b * rs;
     const float k = row_den ? 1.0f / row_den[b] : 1.0f;
     if (act) {
       store_out(S, (int64_t)b * rs + ch0, make_float4(a0[0] * k, a0[1] * k, a0[2] * k, a0[3] * k), wt);
@@ -1161,14 +1069,7 @@ __device__ __forceinline__ bool dense_regime(const link_grid_t &g, int m) {
 // against ~17 per block for the column-walking kernel, and the neighbour ids come from ONE round trip
 // (cell arithmetic + cell_blk) instead of two.  Same summation order on every run: deterministic.
 // ---------------------------------------------------------------------------------------------
-// Optional epilogue of the block gather: the finished row of block `b` goes straight to the rows of the block's voxels
-// (perm[blk_start[b] .. blk_start[b + 1]) = their ids) instead of -- or besides -- the [M, P*C] table: what aux_to_voxel
-// needs (utils.py:84, `new_feat[idx]`), without the table's round trip through memory and the row-gather launch.
-struct bg_scatter_t {
-  const int32_t *blk_start;
-  const int32_t *perm;
-  float *out;                                          // nullptr: no scatter
-};
+// bg_scatter_t (elk_host.h): the optional epilogue of the block gather
 template <int P>
 __device__ __forceinline__ void bg_scatter_row(const bg_scatter_t &sc, uint32_t b, int rs, int c, int ch0, const float4 (&row)[P]) {
   const int p0 = sc.blk_start[b], p1 = sc.blk_start[b + 1];
@@ -1597,76 +1498,121 @@ __global__ void __launch_bounds__(256) k_voxel_demod_ln_g(
   }
 }
 
-static inline int lanes_per_row(int c) {
-  int need = (c + 3) / 4, l = 1;
-  while (l < need) l <<= 1;
-  return l;
+// =============================================================================================
+// Launchers and entries.  Every template axis is chosen by its helper of dispatch.h; the PAIR and DENSE forms are built
+// only for the operators / radius that have them (`if constexpr`), so the set of instantiations is exactly what is listed.
+// =============================================================================================
+
+// channel j and j + C/2 share theta and the row fills its lanes exactly: the PAIR forms (cos and sin only) apply
+static bool row_pairs(const link_elk_desc_t &d, int lpr) {
+  return !(d.flags & LINK_ELK_NO_PAIR) && d.c == 2 * d.cg && d.c == 4 * lpr;
 }
 
-template <int LPR>
-static void launch_modsum_g(int op, hipStream_t st, const float *fin, const int4 *vox, const float *w_pos,
-                            const float *alpha, const int32_t *blk_start, const int32_t *hdr, int c, int cg,
-                            float div, float *S, int64_t m_cap, const float *row_den = nullptr, int flags = 0) {
-  dim3 grid(g_modsum_wgs), block(256);
-  const bool two_part = op == LINK_OP_COS || op == LINK_OP_SIN || op == LINK_OPI_SIN_BWD;
-  const bool pair = !(flags & LINK_ELK_NO_PAIR) && LPR >= 2 && c == 2 * cg && c == 4 * LPR && two_part;
-#define LINK_MS(OPP, PP)                                                                                         \
-  hipLaunchKernelGGL((k_modulate_sum_g<LPR, OPP, PP>), grid, block, 0, st, fin, vox, w_pos, alpha, blk_start, hdr, \
-                     c, cg, div, S, m_cap, g_coop_threshold, (g_wt & 2) != 0 && wt_ok(m_cap + 1, 3 * (int64_t)c), row_den)
-  switch (op) {
-    case LINK_OP_COS: if (pair) LINK_MS(LINK_OP_COS, true); else LINK_MS(LINK_OP_COS, false); break;
-    case LINK_OP_SIN: if (pair) LINK_MS(LINK_OP_SIN, true); else LINK_MS(LINK_OP_SIN, false); break;
-    case LINK_OPI_SIN_BWD: LINK_MS(LINK_OPI_SIN_BWD, false); break;
-    case LINK_OPI_COSX_BWD: LINK_MS(LINK_OPI_COSX_BWD, false); break;
-    default: LINK_MS(LINK_OP_COSX, false); break;
-  }
-#undef LINK_MS
+bool link::modsum_group_path(const link_elk_desc_t *d, hipStream_t st, const float *fin, const int4 *vox,
+                             const float *w_pos, const float *alpha, const int32_t *blk_start, const int32_t *hdr,
+                             float *S_, int64_t m_cap, int op, const float *row_den) {
+  if ((d->flags & LINK_ELK_LANE_CHANNEL) || (d->c & 3) != 0) return false;
+  if (op < 0) op = d->op;
+  const bool wt = (g_wt & 2) != 0 && wt_ok(m_cap + 1, 3 * (int64_t)d->c);
+  return dispatch_lpr(d->c, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    return dispatch_int<LINK_OP_COS, LINK_OP_SIN, LINK_OP_COSX, LINK_OPI_SIN_BWD, LINK_OPI_COSX_BWD>(op, [&](auto o) {
+      constexpr int OP = decltype(o)::value;
+      auto launch = [&](auto pair) {
+        hipLaunchKernelGGL((k_modulate_sum_g<LPR, OP, decltype(pair)::value>), dim3(g_modsum_wgs), dim3(256), 0, st, fin, vox,
+                           w_pos, alpha, blk_start, hdr, d->c, d->cg, d->coord_div, S_, m_cap, g_coop_threshold, wt, row_den);
+      };
+      if constexpr (OP == LINK_OP_COS || OP == LINK_OP_SIN) {
+        if (row_pairs(*d, LPR)) return launch(std::true_type{});
+      }
+      launch(std::false_type{});
+    });
+  });
 }
 
-template <int LPR, int OP>
-static void launch_gdl_g_r(int r, hipStream_t st, int64_t m_cap, const float *S_, const float *fin, const int4 *vox,
-                           const float *w_pos, const float *alpha, const float *ln_w, const float *ln_b,
-                           const int32_t *blk_start, const int4 *blk_coords, const int32_t *cell_blk,
-                           const link_grid_t &g, const int32_t *hdr, const link_elk_desc_t &d, float *out) {
-  dim3 grid(g_gather_wgs), block(256);
-  const bool pair = !(d.flags & LINK_ELK_NO_PAIR) && LPR >= 2 && d.c == 2 * d.cg && d.c == 4 * LPR && OP != LINK_OP_COSX;
-#define LINK_GDLG(RR, PP)                                                                                     \
-  hipLaunchKernelGGL((k_gather_demod_ln_g<LPR, OP, RR, PP>), grid, block, 0, st, S_, fin, vox, w_pos, alpha,  \
-                     ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d.c, d.cg, d.coord_div, d.eps, out, m_cap)
-  if (pair && OP != LINK_OP_COSX) {
-    switch (r) {
-      case 1: LINK_GDLG(1, (OP != LINK_OP_COSX)); break;
-      case 2: LINK_GDLG(2, (OP != LINK_OP_COSX)); break;
-      default: LINK_GDLG(3, (OP != LINK_OP_COSX)); break;
-    }
-  } else {
-    switch (r) {
-      case 1: LINK_GDLG(1, false); break;
-      case 2: LINK_GDLG(2, false); break;
-      default: LINK_GDLG(3, false); break;
-    }
-  }
-#undef LINK_GDLG
+extern "C" int link_modulate_block_sum(const float *fin, const int32_t *vox_sorted, const float *w_pos,
+                                       const float *alpha, const int32_t *blk_start, const int32_t *hdr,
+                                       const link_elk_desc_t *desc, int64_t n, int64_t m_cap, float *S_,
+                                       void *stream) {
+  if (check_desc(desc) != LINK_OK || n < 0 || m_cap < 0) return LINK_ERR_ARG;
+  if (n == 0 || m_cap == 0) return LINK_OK;
+  if (!fin || !vox_sorted || !w_pos || !blk_start || !hdr || !S_) return LINK_ERR_ARG;
+  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
+  hipStream_t st = S(stream);
+  if (modsum_group_path(desc, st, fin, v4, w_pos, alpha, blk_start, hdr, S_, m_cap)) return check_launch("link_modulate_block_sum");
+  const bool ok = dispatch_cpl(desc->c, [&](auto cpl) {
+    constexpr int CPL = decltype(cpl)::value;
+    return dispatch_op(desc->op, [&](auto op) {
+      hipLaunchKernelGGL((k_modulate_sum<CPL, decltype(op)::value>), dim3(g_modsum_wgs), dim3(256), 0, st, fin, v4, w_pos, alpha,
+                         blk_start, hdr, desc->c, desc->cg, desc->coord_div, S_, m_cap);
+    });
+  });
+  return ok ? check_launch("link_modulate_block_sum") : LINK_ERR_ARG;
 }
 
-template <int LPR>
-static void launch_gdl_g(int op, int r, hipStream_t st, int64_t m_cap, const float *S_, const float *fin, const int4 *vox,
-                         const float *w_pos, const float *alpha, const float *ln_w, const float *ln_b,
-                         const int32_t *blk_start, const int4 *blk_coords, const int32_t *cell_blk,
-                         const link_grid_t &g, const int32_t *hdr, const link_elk_desc_t &d, float *out) {
-  if (op == LINK_OP_COS)
-    launch_gdl_g_r<LPR, LINK_OP_COS>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
-  else if (op == LINK_OP_SIN)
-    launch_gdl_g_r<LPR, LINK_OP_SIN>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
-  else
-    launch_gdl_g_r<LPR, LINK_OP_COSX>(r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d, out);
+// the fused gather + de-modulate on the group kernel; false: not a group-kernel shape
+static bool gather_group_path(const link_elk_desc_t *d, hipStream_t st, const float *S_, const float *fin,
+                              const int4 *vox, const float *w_pos, const float *alpha, const float *ln_w,
+                              const float *ln_b, const int32_t *blk_start, const int4 *blk_coords,
+                              const int32_t *cell_blk, const link_grid_t &g, const int32_t *hdr, float *out,
+                              int64_t m_cap) {
+  if ((d->flags & LINK_ELK_LANE_CHANNEL) || (d->c & 3) != 0 || d->r > 3) return false;
+  return dispatch_lpr(d->c, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    return dispatch_op(d->op, [&](auto op) {
+      constexpr int OP = decltype(op)::value;
+      return dispatch_radius(d->r, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        auto launch = [&](auto pair) {
+          hipLaunchKernelGGL((k_gather_demod_ln_g<LPR, OP, R, decltype(pair)::value>), dim3(g_gather_wgs), dim3(256), 0, st, S_,
+                             fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, d->c, d->cg,
+                             d->coord_div, d->eps, out, m_cap);
+        };
+        if constexpr (OP != LINK_OP_COSX) {
+          if (row_pairs(*d, LPR)) return launch(std::true_type{});
+        }
+        launch(std::false_type{});
+      });
+    });
+  });
+}
+
+extern "C" int link_gather_demod_ln(const float *S_, const float *fin, const int32_t *vox_sorted,
+                                    const float *w_pos, const float *alpha, const float *ln_w,
+                                    const float *ln_b, const int32_t *blk_start,
+                                    const int32_t *blk_coords, const int32_t *cell_blk,
+                                    const link_grid_t *grid, const int32_t *hdr,
+                                    const link_elk_desc_t *desc, int64_t n, int64_t m_cap, float *out,
+                                    void *stream) {
+  if (check_desc(desc) != LINK_OK || !grid || n < 0 || m_cap < 0 || desc->r > 5) return LINK_ERR_ARG;
+  if (n == 0 || m_cap == 0) return LINK_OK;
+  if (!S_ || !vox_sorted || !w_pos || !ln_w || !ln_b || !blk_start || !blk_coords || !cell_blk || !hdr || !out)
+    return LINK_ERR_ARG;
+  if (desc->op == LINK_OP_COSX && !fin) return LINK_ERR_ARG;
+  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
+  const int4 *b4 = reinterpret_cast<const int4 *>(blk_coords);
+  hipStream_t st = S(stream);
+  if (gather_group_path(desc, st, S_, fin, v4, w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, out, m_cap))
+    return check_launch("link_gather_demod_ln");
+  const bool ok = dispatch_cpl(desc->c, [&](auto cpl) {
+    constexpr int CPL = decltype(cpl)::value;
+    return dispatch_op(desc->op, [&](auto op) {
+      constexpr int OP = decltype(op)::value;
+      return dispatch_int<1, 2, 3, 4, 5>(desc->r, [&](auto r) {           // the lane = channel kernel is built up to r = 5
+        hipLaunchKernelGGL((k_gather_demod_ln<CPL, OP, decltype(r)::value>), dim3(g_gather_wgs), dim3(256), 0, st, S_, fin, v4,
+                           w_pos, alpha, ln_w, ln_b, blk_start, b4, cell_blk, *grid, hdr, desc->c, desc->cg, desc->coord_div,
+                           desc->eps, out, m_cap);
+      });
+    });
+  });
+  return ok ? check_launch("link_gather_demod_ln") : LINK_ERR_ARG;
 }
 
 template <int LPR, int P>
-static void launch_block_gather(int r, hipStream_t st, const float *S_, const int4 *blk_coords,
+static bool launch_block_gather(int r, hipStream_t st, const float *S_, const int4 *blk_coords,
                                 const int32_t *cell_blk, const link_grid_t &g, const int32_t *hdr, int c,
                                 int64_t m_cap, float *A, int flags, float *den_out, bool allow_dense,
-                                const bg_scatter_t &sc = bg_scatter_t{nullptr, nullptr, nullptr}) {
+                                const bg_scatter_t &sc) {
   const bool wt = (g_wt & 4) != 0 && wt_ok(m_cap + 1, 3 * (int64_t)c);
   unsigned wgs = (unsigned)g_bgather_wgs;
   int tiles_y = 0, tiles_z = 0;
@@ -1685,22 +1631,22 @@ static void launch_block_gather(int r, hipStream_t st, const float *S_, const in
       flags |= 4;
     }
   }
-  dim3 grid(wgs), block(256);
-#define LINK_BGK(RR, DD)                                                                                          \
-  hipLaunchKernelGGL((k_block_gather_g<LPR, P, RR, DD>), grid, block, 0, st, S_, blk_coords, cell_blk, g, hdr, c, \
-                     m_cap, A, wt, flags, den_out, g_bgather_wgs, tiles_y, tiles_z, sc)
-  switch (r) {
-    case 1: LINK_BGK(1, false); break;
-    case 2: LINK_BGK(2, false); break;
-    default: if (flags & 4) LINK_BGK(3, true); else LINK_BGK(3, false); break;
-  }
-#undef LINK_BGK
+  return dispatch_radius(r, [&](auto rr) {
+    constexpr int R = decltype(rr)::value;
+    auto launch = [&](auto dense) {
+      hipLaunchKernelGGL((k_block_gather_g<LPR, P, R, decltype(dense)::value>), dim3(wgs), dim3(256), 0, st, S_, blk_coords,
+                         cell_blk, g, hdr, c, m_cap, A, wt, flags, den_out, g_bgather_wgs, tiles_y, tiles_z, sc);
+    };
+    if constexpr (R == 3) {
+      if (flags & 4) return launch(std::true_type{});
+    }
+    launch(std::false_type{});
+  });
 }
 
-static int block_gather_impl(const float *S_, const int32_t *blk_coords, const int32_t *cell_blk,
-                             const link_grid_t *grid, const int32_t *hdr, const link_elk_desc_t *desc,
-                             int64_t m_cap, float *A, int flags, float *den_out, void *stream,
-                             const bg_scatter_t &sc = bg_scatter_t{nullptr, nullptr, nullptr}) {
+int link::block_gather_impl(const float *S_, const int32_t *blk_coords, const int32_t *cell_blk,
+                            const link_grid_t *grid, const int32_t *hdr, const link_elk_desc_t *desc,
+                            int64_t m_cap, float *A, int flags, float *den_out, void *stream, const bg_scatter_t &sc) {
   if (check_desc(desc) != LINK_OK || !grid || m_cap < 0 || desc->r > 3 || (desc->c & 3) != 0) return LINK_ERR_ARG;
   if (m_cap == 0) return LINK_OK;
   if (!S_ || !blk_coords || !cell_blk || !hdr || (!A && !sc.out)) return LINK_ERR_ARG;
@@ -1708,20 +1654,14 @@ static int block_gather_impl(const float *S_, const int32_t *blk_coords, const i
   if ((m_cap + 1) * (int64_t)(desc->c * 3 + 1) * 4 >= (1LL << 32)) return LINK_ERR_ARG;   // 32-bit row offsets
   const int4 *b4 = reinterpret_cast<const int4 *>(blk_coords);
   hipStream_t st = S(stream);
-  const bool p3 = desc->op == LINK_OP_COSX;
   const bool dense_ok = !(desc->flags & LINK_ELK_NO_DENSE_GRID);
-#define LINK_BG(L)                                                                                                   \
-  if (p3) launch_block_gather<L, 3>(desc->r, st, S_, b4, cell_blk, *grid, hdr, desc->c, m_cap, A, flags, den_out, dense_ok, sc); \
-  else launch_block_gather<L, 2>(desc->r, st, S_, b4, cell_blk, *grid, hdr, desc->c, m_cap, A, flags, den_out, dense_ok, sc)
-  switch (lanes_per_row(desc->c)) {
-    case 1: case 2: case 4: LINK_BG(4); break;
-    case 8: LINK_BG(8); break;
-    case 16: LINK_BG(16); break;
-    case 32: LINK_BG(32); break;
-    default: LINK_BG(64); break;
-  }
-#undef LINK_BG
-  return check_launch("link_block_gather");
+  const bool ok = dispatch_lpr(desc->c, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    if (desc->op == LINK_OP_COSX)
+      return launch_block_gather<LPR, 3>(desc->r, st, S_, b4, cell_blk, *grid, hdr, desc->c, m_cap, A, flags, den_out, dense_ok, sc);
+    return launch_block_gather<LPR, 2>(desc->r, st, S_, b4, cell_blk, *grid, hdr, desc->c, m_cap, A, flags, den_out, dense_ok, sc);
+  });
+  return ok ? check_launch("link_block_gather") : LINK_ERR_ARG;
 }
 
 extern "C" int link_block_gather(const float *S_, const int32_t *blk_coords, const int32_t *cell_blk,
@@ -1730,29 +1670,36 @@ extern "C" int link_block_gather(const float *S_, const int32_t *blk_coords, con
   return block_gather_impl(S_, blk_coords, cell_blk, grid, hdr, desc, m_cap, A, 0, nullptr, stream);
 }
 
-template <int LPR>
-static void launch_voxel_demod(const link_elk_desc_t &d, int64_t n, hipStream_t st, const float *A,
-                               const float *fin, const int4 *vox, const int32_t *pos_blk, const float *w_pos,
-                               const float *alpha, const float *ln_w, const float *ln_b, const int32_t *hdr,
-                               float *out) {
-  constexpr int G = 64 / LPR;
-  const bool pair = !(d.flags & LINK_ELK_NO_PAIR) && LPR >= 2 && d.c == 2 * d.cg && d.c == 4 * LPR && d.op != LINK_OP_COSX;
-  const int64_t groups = pair ? (n + 1) / 2 : n;
-  const int64_t wgs = (groups + 4 * G - 1) / (4 * G);
-  dim3 grid((unsigned)wgs), block(256);
-#define LINK_VD(OPP, PP)                                                                                  \
-  hipLaunchKernelGGL((k_voxel_demod_ln_g<LPR, OPP, PP>), grid, block, 0, st, A, fin, vox, pos_blk, w_pos,  \
-                     alpha, ln_w, ln_b, hdr, d.c, d.cg, d.coord_div, d.eps, out, (g_wt & 8) != 0 && wt_ok(n, d.c))
-  if (d.op == LINK_OP_COS) { if (pair) LINK_VD(LINK_OP_COS, true); else LINK_VD(LINK_OP_COS, false); }
-  else if (d.op == LINK_OP_SIN) { if (pair) LINK_VD(LINK_OP_SIN, true); else LINK_VD(LINK_OP_SIN, false); }
-  else LINK_VD(LINK_OP_COSX, false);
-#undef LINK_VD
+int link::voxel_demod_impl(const float *A, const float *fin, const int32_t *vox_sorted,
+                           const int32_t *pos_blk, const float *w_pos, const float *alpha,
+                           const float *ln_w, const float *ln_b, const int32_t *hdr,
+                           const link_elk_desc_t *desc, int64_t n, float *out, void *stream) {
+  if (check_desc(desc) != LINK_OK || n < 0 || (desc->c & 3) != 0) return LINK_ERR_ARG;
+  if (n == 0) return LINK_OK;
+  if (!A || !vox_sorted || !pos_blk || !w_pos || !hdr || !out) return LINK_ERR_ARG;
+  if (desc->op == LINK_OP_COSX && !fin) return LINK_ERR_ARG;
+  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
+  hipStream_t st = S(stream);
+  const link_elk_desc_t &d = *desc;
+  const bool wt = (g_wt & 8) != 0 && wt_ok(n, d.c);
+  const bool ok = dispatch_lpr(d.c, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value, G = 64 / LPR;
+    return dispatch_op(d.op, [&](auto op) {
+      constexpr int OP = decltype(op)::value;
+      auto launch = [&](auto pair) {                 // one group per voxel, or per two with PAIR
+        const int64_t groups = decltype(pair)::value ? (n + 1) / 2 : n;
+        hipLaunchKernelGGL((k_voxel_demod_ln_g<LPR, OP, decltype(pair)::value>), dim3((unsigned)((groups + 4 * G - 1) / (4 * G))),
+                           dim3(256), 0, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, d.c, d.cg, d.coord_div, d.eps,
+                           out, wt);
+      };
+      if constexpr (OP != LINK_OP_COSX) {
+        if (row_pairs(d, LPR)) return launch(std::true_type{});
+      }
+      launch(std::false_type{});
+    });
+  });
+  return ok ? check_launch("link_voxel_demod_ln") : LINK_ERR_ARG;
 }
-
-static int voxel_demod_impl(const float *A, const float *fin, const int32_t *vox_sorted,
-                            const int32_t *pos_blk, const float *w_pos, const float *alpha,
-                            const float *ln_w, const float *ln_b, const int32_t *hdr,
-                            const link_elk_desc_t *desc, int64_t n, float *out, void *stream);
 
 extern "C" int link_voxel_demod_ln(const float *A, const float *fin, const int32_t *vox_sorted,
                                    const int32_t *pos_blk, const float *w_pos, const float *alpha,
@@ -1760,866 +1707,6 @@ extern "C" int link_voxel_demod_ln(const float *A, const float *fin, const int32
                                    const link_elk_desc_t *desc, int64_t n, float *out, void *stream) {
   if (!ln_w || !ln_b) return LINK_ERR_ARG;
   return voxel_demod_impl(A, fin, vox_sorted, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, desc, n, out, stream);
-}
-
-// ln_w == NULL: no LayerNorm (the training forward, whose LayerNorm is differentiated by the host)
-static int voxel_demod_impl(const float *A, const float *fin, const int32_t *vox_sorted,
-                            const int32_t *pos_blk, const float *w_pos, const float *alpha,
-                            const float *ln_w, const float *ln_b, const int32_t *hdr,
-                            const link_elk_desc_t *desc, int64_t n, float *out, void *stream) {
-  if (check_desc(desc) != LINK_OK || n < 0 || (desc->c & 3) != 0) return LINK_ERR_ARG;
-  if (n == 0) return LINK_OK;
-  if (!A || !vox_sorted || !pos_blk || !w_pos || !hdr || !out) return LINK_ERR_ARG;
-  if (desc->op == LINK_OP_COSX && !fin) return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  hipStream_t st = S(stream);
-  switch (lanes_per_row(desc->c)) {
-    case 1: case 2: case 4: launch_voxel_demod<4>(*desc, n, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, out); break;
-    case 8: launch_voxel_demod<8>(*desc, n, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, out); break;
-    case 16: launch_voxel_demod<16>(*desc, n, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, out); break;
-    case 32: launch_voxel_demod<32>(*desc, n, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, out); break;
-    default: launch_voxel_demod<64>(*desc, n, st, A, fin, v4, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, out); break;
-  }
-  return check_launch("link_voxel_demod_ln");
-}
-
-static bool modsum_group_path(const link_elk_desc_t *d, hipStream_t st, const float *fin, const int4 *vox,
-                              const float *w_pos, const float *alpha, const int32_t *blk_start,
-                              const int32_t *hdr, float *S_, int64_t m_cap, int op, const float *row_den) {
-  if ((d->flags & LINK_ELK_LANE_CHANNEL) || (d->c & 3) != 0) return false;
-  if (op < 0) op = d->op;
-#define LINK_MSG(L) launch_modsum_g<L>(op, st, fin, vox, w_pos, alpha, blk_start, hdr, d->c, d->cg, d->coord_div, S_, m_cap, row_den, d->flags)
-  switch (lanes_per_row(d->c)) {
-    case 1: case 2: case 4: LINK_MSG(4); break;
-    case 8: LINK_MSG(8); break;
-    case 16: LINK_MSG(16); break;
-    case 32: LINK_MSG(32); break;
-    default: LINK_MSG(64); break;
-  }
-#undef LINK_MSG
-  return true;
-}
-
-static bool gather_group_path(const link_elk_desc_t *d, hipStream_t st, const float *S_, const float *fin,
-                              const int4 *vox, const float *w_pos, const float *alpha, const float *ln_w,
-                              const float *ln_b, const int32_t *blk_start, const int4 *blk_coords,
-                              const int32_t *cell_blk, const link_grid_t &g, const int32_t *hdr, float *out,
-                              int64_t m_cap) {
-  if ((d->flags & LINK_ELK_LANE_CHANNEL) || (d->c & 3) != 0 || d->r > 3) return false;
-  switch (lanes_per_row(d->c)) {
-    case 1: case 2: case 4: launch_gdl_g<4>(d->op, d->r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, *d, out); break;
-    case 8: launch_gdl_g<8>(d->op, d->r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, *d, out); break;
-    case 16: launch_gdl_g<16>(d->op, d->r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, *d, out); break;
-    case 32: launch_gdl_g<32>(d->op, d->r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, *d, out); break;
-    default: launch_gdl_g<64>(d->op, d->r, st, m_cap, S_, fin, vox, w_pos, alpha, ln_w, ln_b, blk_start, blk_coords, cell_blk, g, hdr, *d, out); break;
-  }
-  return true;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Training form of the middle of R_core:  new = demodulate(aggregate(modulate(fin, theta)), theta)
-// (linkunet.py:151-176 between pre_mix and self.norm), forward and backward.  The two LayerNorms and
-// the pre_mix Linear stay with the host framework's autograd (library GEMM + its LayerNorm).
-//
-// Backward, per part (v = A[block(i)], X = modulated features, g = grad(new)):
-//   gA[m]   = (1/den[m]) * sum_{i in m} g_i * d(new)/d(v)          -> the forward's modulate+block-sum kernel
-//             with the backward factors ([cos, sin] | [cos, -sin] | [cos, sin, 1]) and a row scale
-//   gS[n]   = sum_{m : n in region(m)} gA[m]                       -> the forward's block gather, transposed
-//             neighbourhood, no normalisation
-//   g_fin_i = gS[block(i)] . d(X)/d(fin)  (+ the -theta*g term of cos_x), and the theta gradient folded
-//             into per-workgroup partial sums of d/d(alpha) and d/d(pos_weight)  -> k_voxel_bwd_g
-// ---------------------------------------------------------------------------------------------
-template <int LPR, int OP>
-__global__ void __launch_bounds__(256) k_voxel_bwd_g(
-    const float *__restrict__ gS, const float *__restrict__ A_tab, const float *__restrict__ fin,
-    const float *__restrict__ g_new, const int4 *__restrict__ vox_sorted, const int32_t *__restrict__ pos_blk,
-    const float *__restrict__ w_pos, const float *__restrict__ alpha, const int32_t *__restrict__ hdr, int c,
-    int cg, float coord_div, float *__restrict__ g_fin, float *__restrict__ partials) {
-  constexpr int P = (OP == LINK_OP_COSX) ? 3 : 2;
-  constexpr int G = 64 / LPR;
-  __shared__ float red[4][16][LPR];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & (LPR - 1);
-  const int ch0 = 4 * li;
-  const bool act = ch0 < c;
-  const int cofs = act ? ch0 : 0;
-  const int n = hdr[LINK_HDR_NVALID];
-  const int ra = P * c;
-  float w0[4], w1[4], w2[4], al[4];
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    int tc = act ? (ch0 + e) % cg : 0;
-    w0[e] = w_pos[3 * tc + 0]; w1[e] = w_pos[3 * tc + 1]; w2[e] = w_pos[3 * tc + 2];
-    al[e] = alpha ? alpha[tc] : 1.0f;
-  }
-  float acc[4][4];                                 // [d alpha | d w.x | d w.y | d w.z][channel of the lane]
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-#pragma unroll
-    for (int e = 0; e < 4; e++) acc[q][e] = 0.f;
-  const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
-  for (int64_t p = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; p < n; p += ngroups) {
-    const int4 rc = vox_sorted[p];
-    const int b = pos_blk[p];
-    float4 gx4[P], av4[P];
-#pragma unroll
-    for (int pp = 0; pp < P; pp++) {
-      gx4[pp] = *reinterpret_cast<const float4 *>(&gS[(int64_t)b * ra + pp * c + cofs]);
-      av4[pp] = *reinterpret_cast<const float4 *>(&A_tab[(int64_t)b * ra + pp * c + cofs]);
-    }
-    const float4 f4 = *reinterpret_cast<const float4 *>(&fin[(int64_t)rc.w * c + cofs]);
-    const float4 g4 = *reinterpret_cast<const float4 *>(&g_new[(int64_t)rc.w * c + cofs]);
-    float x = (float)rc.x, y = (float)rc.y, z = (float)rc.z;
-    if (coord_div != 1.0f) { x = x / coord_div; y = y / coord_div; z = z / coord_div; }
-    const float fv[4] = {f4.x, f4.y, f4.z, f4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
-    const float gx0[4] = {gx4[0].x, gx4[0].y, gx4[0].z, gx4[0].w}, gx1[4] = {gx4[1].x, gx4[1].y, gx4[1].z, gx4[1].w};
-    const float gx2[4] = {gx4[P - 1].x, gx4[P - 1].y, gx4[P - 1].z, gx4[P - 1].w};
-    const float v0[4] = {av4[0].x, av4[0].y, av4[0].z, av4[0].w}, v1[4] = {av4[1].x, av4[1].y, av4[1].z, av4[1].w};
-    float gf[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const float t = fmaf(z, w2[e], fmaf(y, w1[e], x * w0[e]));
-      const float th = t * al[e];
-      float sn, cs;
-      sincos_fast(th, sn, cs);
-      float g_cs, g_sn, gth;
-      if (OP == LINK_OP_SIN) {                     // new = v0 cos - v1 sin ; X = [f sin, f cos]
-        gf[e] = gx0[e] * sn + gx1[e] * cs;
-        g_cs = gv[e] * v0[e] + gx1[e] * fv[e];
-        g_sn = gx0[e] * fv[e] - gv[e] * v1[e];
-      } else {                                     // new = v0 cos + v1 sin (+ v2 - f theta) ; X = [f cos, f sin, (f theta)]
-        gf[e] = gx0[e] * cs + gx1[e] * sn;
-        g_cs = gv[e] * v0[e] + gx0[e] * fv[e];
-        g_sn = gv[e] * v1[e] + gx1[e] * fv[e];
-      }
-      gth = cs * g_sn - sn * g_cs;
-      if (OP == LINK_OP_COSX) {
-        const float d = gx2[e] - gv[e];
-        gf[e] = fmaf(d, th, gf[e]);
-        gth = fmaf(d, fv[e], gth);
-      }
-      if (act) {
-        acc[0][e] = fmaf(gth, t, acc[0][e]);
-        const float ga = gth * al[e];
-        acc[1][e] = fmaf(ga, x, acc[1][e]);
-        acc[2][e] = fmaf(ga, y, acc[2][e]);
-        acc[3][e] = fmaf(ga, z, acc[3][e]);
-      }
-    }
-    if (act) *reinterpret_cast<float4 *>(&g_fin[(int64_t)rc.w * c + ch0]) = make_float4(gf[0], gf[1], gf[2], gf[3]);
-  }
-  // fixed reduction tree: groups of the wave, then the 4 waves through LDS -> one partial row per workgroup
-#pragma unroll
-  for (int o = LPR; o < 64; o <<= 1)
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-      for (int e = 0; e < 4; e++) acc[q][e] += __shfl_xor(acc[q][e], o, 64);
-  if (lane < LPR)
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-      for (int e = 0; e < 4; e++) red[wave][q * 4 + e][li] = acc[q][e];
-  __syncthreads();
-  if (wave == 0 && lane < LPR && act) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      float4 o;
-      o.x = (red[0][q * 4 + 0][li] + red[1][q * 4 + 0][li]) + (red[2][q * 4 + 0][li] + red[3][q * 4 + 0][li]);
-      o.y = (red[0][q * 4 + 1][li] + red[1][q * 4 + 1][li]) + (red[2][q * 4 + 1][li] + red[3][q * 4 + 1][li]);
-      o.z = (red[0][q * 4 + 2][li] + red[1][q * 4 + 2][li]) + (red[2][q * 4 + 2][li] + red[3][q * 4 + 2][li]);
-      o.w = (red[0][q * 4 + 3][li] + red[1][q * 4 + 3][li]) + (red[2][q * 4 + 3][li] + red[3][q * 4 + 3][li]);
-      *reinterpret_cast<float4 *>(&partials[((int64_t)blockIdx.x * 4 + q) * c + ch0]) = o;
-    }
-  }
-}
-
-template <int LPR>
-static void launch_voxel_bwd(const link_elk_desc_t &d, int wgs, hipStream_t st, const float *gS, const float *A,
-                             const float *fin, const float *g_new, const int4 *vox, const int32_t *pos_blk,
-                             const float *w_pos, const float *alpha, const int32_t *hdr, float *g_fin,
-                             float *partials) {
-  dim3 grid(wgs), block(256);
-#define LINK_VB(OPP)                                                                                          \
-  hipLaunchKernelGGL((k_voxel_bwd_g<LPR, OPP>), grid, block, 0, st, gS, A, fin, g_new, vox, pos_blk, w_pos,    \
-                     alpha, hdr, d.c, d.cg, d.coord_div, g_fin, partials)
-  if (d.op == LINK_OP_COS) LINK_VB(LINK_OP_COS);
-  else if (d.op == LINK_OP_SIN) LINK_VB(LINK_OP_SIN);
-  else LINK_VB(LINK_OP_COSX);
-#undef LINK_VB
-}
-
-// Backward of self.norm fused with the recomputation of its input: new_i is rebuilt from the saved A
-// row of the voxel's block exactly as the forward's voxel kernel builds it (same operation order), its
-// LayerNorm statistics are recomputed, and g_new = rstd * (gy*w - mean(gy*w) - xhat * mean(gy*w*xhat)).
-// Per-workgroup partial sums of d/d(norm.weight) = sum gy*xhat and d/d(norm.bias) = sum gy.
-template <int LPR, int OP>
-__global__ void __launch_bounds__(256) k_out_ln_bwd_g(
-    const float *__restrict__ g_out, const float *__restrict__ A_tab, const float *__restrict__ fin,
-    const int4 *__restrict__ vox_sorted, const int32_t *__restrict__ pos_blk, const float *__restrict__ w_pos,
-    const float *__restrict__ alpha, const float *__restrict__ ln_w, const int32_t *__restrict__ hdr, int c,
-    int cg, float coord_div, float eps, float *__restrict__ g_new, float *__restrict__ partials) {
-  constexpr int P = (OP == LINK_OP_COSX) ? 3 : 2;
-  constexpr int G = 64 / LPR;
-  __shared__ float red[4][8][LPR];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & (LPR - 1);
-  const int ch0 = 4 * li;
-  const bool act = ch0 < c;
-  const int cofs = act ? ch0 : 0;
-  const int n = hdr[LINK_HDR_NVALID];
-  const int ra = P * c;
-  const float inv_c = 1.0f / (float)c;
-  float w0[4], w1[4], w2[4], al[4], gw[4];
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    int ch = act ? ch0 + e : 0;
-    int tc = ch % cg;
-    w0[e] = w_pos[3 * tc + 0]; w1[e] = w_pos[3 * tc + 1]; w2[e] = w_pos[3 * tc + 2];
-    al[e] = alpha ? alpha[tc] : 1.0f;
-    gw[e] = ln_w[ch];
-  }
-  float aw[4] = {0.f, 0.f, 0.f, 0.f}, ab[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
-  for (int64_t p = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; p < n; p += ngroups) {
-    const int4 rc = vox_sorted[p];
-    const int b = pos_blk[p];
-    float4 av4[P];
-#pragma unroll
-    for (int pp = 0; pp < P; pp++) av4[pp] = *reinterpret_cast<const float4 *>(&A_tab[(int64_t)b * ra + pp * c + cofs]);
-    float4 f4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (OP == LINK_OP_COSX) f4 = *reinterpret_cast<const float4 *>(&fin[(int64_t)rc.w * c + cofs]);
-    const float4 g4 = *reinterpret_cast<const float4 *>(&g_out[(int64_t)rc.w * c + cofs]);
-    float x = (float)rc.x, y = (float)rc.y, z = (float)rc.z;
-    if (coord_div != 1.0f) { x = x / coord_div; y = y / coord_div; z = z / coord_div; }
-    const float v0[4] = {av4[0].x, av4[0].y, av4[0].z, av4[0].w}, v1[4] = {av4[1].x, av4[1].y, av4[1].z, av4[1].w};
-    const float v2[4] = {av4[P - 1].x, av4[P - 1].y, av4[P - 1].z, av4[P - 1].w};
-    const float fv[4] = {f4.x, f4.y, f4.z, f4.w}, gy[4] = {g4.x, g4.y, g4.z, g4.w};
-    float nv[4], sm = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const float th = theta_of(x, y, z, w0[e], w1[e], w2[e], al[e]);
-      float sn, cs;
-      sincos_fast(th, sn, cs);
-      float va;
-      if (OP == LINK_OP_SIN) va = __fsub_rn(__fmul_rn(v0[e], cs), __fmul_rn(v1[e], sn));
-      else va = __fadd_rn(__fmul_rn(v0[e], cs), __fmul_rn(v1[e], sn));
-      if (OP == LINK_OP_COSX) va = __fadd_rn(va, __fsub_rn(v2[e], link_mul_rn(fv[e], th)));
-      nv[e] = act ? va : 0.f;
-      sm += nv[e];
-    }
-    const float mean = grp_sum<LPR>(sm) * inv_c;
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) { const float d = act ? nv[e] - mean : 0.f; q += d * d; }
-    const float rstd = 1.0f / sqrtf(grp_sum<LPR>(q) * inv_c + eps);
-    float xh[4], gx[4], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      xh[e] = act ? (nv[e] - mean) * rstd : 0.f;
-      gx[e] = act ? gy[e] * gw[e] : 0.f;
-      s1 += gx[e];
-      s2 = fmaf(gx[e], xh[e], s2);
-      if (act) { aw[e] = fmaf(gy[e], xh[e], aw[e]); ab[e] += gy[e]; }
-    }
-    const float m1 = grp_sum<LPR>(s1) * inv_c, m2 = grp_sum<LPR>(s2) * inv_c;
-    if (act) {
-      float4 o;
-      o.x = rstd * (gx[0] - m1 - xh[0] * m2);
-      o.y = rstd * (gx[1] - m1 - xh[1] * m2);
-      o.z = rstd * (gx[2] - m1 - xh[2] * m2);
-      o.w = rstd * (gx[3] - m1 - xh[3] * m2);
-      *reinterpret_cast<float4 *>(&g_new[(int64_t)rc.w * c + ch0]) = o;
-    }
-  }
-#pragma unroll
-  for (int o = LPR; o < 64; o <<= 1)
-#pragma unroll
-    for (int e = 0; e < 4; e++) { aw[e] += __shfl_xor(aw[e], o, 64); ab[e] += __shfl_xor(ab[e], o, 64); }
-  if (lane < LPR)
-#pragma unroll
-    for (int e = 0; e < 4; e++) { red[wave][e][li] = aw[e]; red[wave][4 + e][li] = ab[e]; }
-  __syncthreads();
-  if (wave == 0 && lane < LPR && act) {
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      float4 o;
-      o.x = (red[0][q * 4 + 0][li] + red[1][q * 4 + 0][li]) + (red[2][q * 4 + 0][li] + red[3][q * 4 + 0][li]);
-      o.y = (red[0][q * 4 + 1][li] + red[1][q * 4 + 1][li]) + (red[2][q * 4 + 1][li] + red[3][q * 4 + 1][li]);
-      o.z = (red[0][q * 4 + 2][li] + red[1][q * 4 + 2][li]) + (red[2][q * 4 + 2][li] + red[3][q * 4 + 2][li]);
-      o.w = (red[0][q * 4 + 3][li] + red[1][q * 4 + 3][li]) + (red[2][q * 4 + 3][li] + red[3][q * 4 + 3][li]);
-      *reinterpret_cast<float4 *>(&partials[((int64_t)blockIdx.x * 2 + q) * c + ch0]) = o;
-    }
-  }
-}
-
-template <int LPR>
-static void launch_out_ln_bwd(const link_elk_desc_t &d, int wgs, hipStream_t st, const float *g_out, const float *A,
-                              const float *fin, const int4 *vox, const int32_t *pos_blk, const float *w_pos,
-                              const float *alpha, const float *ln_w, const int32_t *hdr, float *g_new,
-                              float *partials) {
-  dim3 grid(wgs), block(256);
-#define LINK_OB(OPP)                                                                                         \
-  hipLaunchKernelGGL((k_out_ln_bwd_g<LPR, OPP>), grid, block, 0, st, g_out, A, fin, vox, pos_blk, w_pos,      \
-                     alpha, ln_w, hdr, d.c, d.cg, d.coord_div, d.eps, g_new, partials)
-  if (d.op == LINK_OP_COS) LINK_OB(LINK_OP_COS);
-  else if (d.op == LINK_OP_SIN) LINK_OB(LINK_OP_SIN);
-  else LINK_OB(LINK_OP_COSX);
-#undef LINK_OB
-}
-
-// Backward of pre_mix = LayerNorm(F @ Wpre^T): the pre-LayerNorm activations are RECOMPUTED with the
-// forward's MFMA schedule (so the statistics are bit-identical to the forward's), the LayerNorm backward
-// is applied in the accumulator layout (lane = 4 channels x 4 tiles of one voxel), and
-// g_F = g_pre @ Wpre runs as a second MFMA pass whose B operand IS that accumulator layout and whose A
-// operand is a transposed copy of W in LDS.  g_pre is also stored (the weight gradient
-// g_pre^T @ F is a plain GEMM left to the library), and per-workgroup partial sums of
-// d/d(pre_mix.1.weight) = sum g_fin*xhat and d/d(pre_mix.1.bias) = sum g_fin are written.
-// IO (row_io.h): type of feats (read) and g_feats (written); g_fin, g_pre and the partials stay fp32.
-template <int C, int IO = LINK_IO_F32>
-__global__ void __launch_bounds__(256) k_premix_ln_bwd(const void *__restrict__ feats,
-                                                       const float *__restrict__ w_pre,
-                                                       const float *__restrict__ ln_w,
-                                                       const float *__restrict__ g_fin, int64_t n, float eps,
-                                                       float *__restrict__ g_pre, void *__restrict__ g_feats,
-                                                       float *__restrict__ partials) {
-  constexpr int T = C / 16;
-  constexpr int LDW = C + 4;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float *w_lds = reinterpret_cast<float *>(smem_raw);          // W   [j][k]
-  float *wt_lds = w_lds + C * LDW;                             // W^T [k][j]
-  float *red = wt_lds + C * LDW;                               // [4 waves][2][C]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, g = lane >> 4;
-  for (int e = tid * 4; e < C * C; e += 256 * 4) {
-    int r = e / C, col = e - r * C;
-    const float4 w4 = *reinterpret_cast<const float4 *>(&w_pre[e]);
-    *reinterpret_cast<float4 *>(&w_lds[r * LDW + col]) = w4;
-    wt_lds[(col + 0) * LDW + r] = w4.x; wt_lds[(col + 1) * LDW + r] = w4.y;
-    wt_lds[(col + 2) * LDW + r] = w4.z; wt_lds[(col + 3) * LDW + r] = w4.w;
-  }
-  __syncthreads();
-  float lw[T][4];
-#pragma unroll
-  for (int tp = 0; tp < T; tp++) {
-    const float4 l4 = *reinterpret_cast<const float4 *>(&ln_w[16 * tp + 4 * g]);
-    lw[tp][0] = l4.x; lw[tp][1] = l4.y; lw[tp][2] = l4.z; lw[tp][3] = l4.w;
-  }
-  float pw[T][4], pb[T][4];
-#pragma unroll
-  for (int tp = 0; tp < T; tp++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) pw[tp][r] = pb[tp][r] = 0.f;
-  const int64_t tiles = (n + 15) / 16;
-  for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < tiles; tile += (int64_t)gridDim.x * 4) {
-    const int64_t v = tile * 16 + li;
-    const bool ok = v < n;
-    const int64_t vl = ok ? v : n - 1;
-    float4 f[T], gf4[T];
-#pragma unroll
-    for (int t = 0; t < T; t++) f[t] = row_ld4<IO>(feats, vl * C + 16 * t + 4 * g);
-#pragma unroll
-    for (int t = 0; t < T; t++) gf4[t] = *reinterpret_cast<const float4 *>(&g_fin[vl * C + 16 * t + 4 * g]);
-    floatx4 acc[T];
-#pragma unroll
-    for (int tp = 0; tp < T; tp++) acc[tp] = (floatx4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < T; t++) {
-#pragma unroll
-      for (int tp = 0; tp < T; tp++) {
-        float4 a = *reinterpret_cast<const float4 *>(&w_lds[(16 * tp + li) * LDW + 16 * t + 4 * g]);
-        acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f[t].x, acc[tp], 0, 0, 0);
-        acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f[t].y, acc[tp], 0, 0, 0);
-        acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f[t].z, acc[tp], 0, 0, 0);
-        acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f[t].w, acc[tp], 0, 0, 0);
-      }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int tp = 0; tp < T; tp++) s += (acc[tp][0] + acc[tp][1]) + (acc[tp][2] + acc[tp][3]);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int tp = 0; tp < T; tp++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        float d = acc[tp][r] - mean;
-        q += d * d;
-      }
-    q += __shfl_xor(q, 16, 64);
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = 1.0f / sqrtf(q * (1.0f / C) + eps);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int tp = 0; tp < T; tp++) {
-      const float gv[4] = {gf4[tp].x, gf4[tp].y, gf4[tp].z, gf4[tp].w};
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const float xh = (acc[tp][r] - mean) * rstd;
-        const float gx = gv[r] * lw[tp][r];
-        s1 += gx;
-        s2 = fmaf(gx, xh, s2);
-        if (ok) { pw[tp][r] = fmaf(gv[r], xh, pw[tp][r]); pb[tp][r] += gv[r]; }
-        acc[tp][r] = xh;                            // keep xhat; gx is recomputed below (saves 16 VGPRs)
-      }
-    }
-    s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
-    const float m1 = s1 * (1.0f / C), m2 = s2 * (1.0f / C);
-#pragma unroll
-    for (int tp = 0; tp < T; tp++) {
-      const float gv[4] = {gf4[tp].x, gf4[tp].y, gf4[tp].z, gf4[tp].w};
-#pragma unroll
-      for (int r = 0; r < 4; r++) acc[tp][r] = rstd * (gv[r] * lw[tp][r] - m1 - acc[tp][r] * m2);   // g_pre
-      if (ok)
-        *reinterpret_cast<float4 *>(&g_pre[v * C + 16 * tp + 4 * g]) = make_float4(acc[tp][0], acc[tp][1], acc[tp][2], acc[tp][3]);
-    }
-    // g_F[v][k] = sum_j g_pre[v][j] W[j][k]:  D2[k][v] = sum_j W^T[k][j] g_pre[v][j]
-    floatx4 acc2[T];
-#pragma unroll
-    for (int tp = 0; tp < T; tp++) acc2[tp] = (floatx4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < T; t++) {
-#pragma unroll
-      for (int tp = 0; tp < T; tp++) {
-        float4 a = *reinterpret_cast<const float4 *>(&wt_lds[(16 * tp + li) * LDW + 16 * t + 4 * g]);
-        acc2[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, acc[t][0], acc2[tp], 0, 0, 0);
-        acc2[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, acc[t][1], acc2[tp], 0, 0, 0);
-        acc2[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, acc[t][2], acc2[tp], 0, 0, 0);
-        acc2[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, acc[t][3], acc2[tp], 0, 0, 0);
-      }
-    }
-    if (ok) {
-#pragma unroll
-      for (int tp = 0; tp < T; tp++)
-        row_st4<IO>(g_feats, v * C + 16 * tp + 4 * g, make_float4(acc2[tp][0], acc2[tp][1], acc2[tp][2], acc2[tp][3]));
-    }
-  }
-  // LayerNorm parameter gradients: sum over the 16 voxel lanes of each quarter-wave, then over waves
-#pragma unroll
-  for (int tp = 0; tp < T; tp++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      pw[tp][r] = grp_sum<16>(pw[tp][r]);
-      pb[tp][r] = grp_sum<16>(pb[tp][r]);
-    }
-  if (li == 0) {
-#pragma unroll
-    for (int tp = 0; tp < T; tp++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        red[(wave * 2 + 0) * C + 16 * tp + 4 * g + r] = pw[tp][r];
-        red[(wave * 2 + 1) * C + 16 * tp + 4 * g + r] = pb[tp][r];
-      }
-  }
-  __syncthreads();
-  for (int e = tid; e < 2 * C; e += 256) {
-    const int qq = e / C, ch = e - qq * C;
-    partials[((int64_t)blockIdx.x * 2 + qq) * C + ch] =
-        (red[(0 * 2 + qq) * C + ch] + red[(1 * 2 + qq) * C + ch]) + (red[(2 * 2 + qq) * C + ch] + red[(3 * 2 + qq) * C + ch]);
-  }
-}
-
-template <int C, int IO = LINK_IO_F32>
-static int launch_premix_bwd(const void *feats, const float *w_pre, const float *ln_w, const float *g_fin,
-                             int64_t n, float eps, float *g_pre, void *g_feats, float *partials, int wgs,
-                             hipStream_t st) {
-  size_t lds = ((size_t)2 * C * (C + 4) + 8 * C) * sizeof(float);
-  if (lds > 64 * 1024) {
-    // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
-    // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_bwd<C, IO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL((k_premix_ln_bwd<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, g_fin, n, eps,
-                     g_pre, g_feats, partials);
-  return check_launch("link_premix_ln_backward");
-}
-
-extern "C" int32_t link_elk_mid_partial_rows(void) { return 1024; }
-
-extern "C" int link_premix_ln_backward(const float *feats, const float *w_pre, const float *ln_w,
-                                       const float *g_fin, int64_t n, int32_t c, float eps, float *g_pre,
-                                       float *g_feats, float *partials, void *stream) {
-  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;     // MFMA path only; callers fall back
-  if (n == 0) return LINK_OK;
-  if (!feats || !w_pre || !ln_w || !g_fin || !g_pre || !g_feats || !partials) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  const int wgs = link_elk_mid_partial_rows();
-  switch (c) {
-    case 16: return launch_premix_bwd<16>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 32: return launch_premix_bwd<32>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 48: return launch_premix_bwd<48>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 64: return launch_premix_bwd<64>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 80: return launch_premix_bwd<80>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 96: return launch_premix_bwd<96>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 112: return launch_premix_bwd<112>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    default: return launch_premix_bwd<128>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-  }
-}
-
-extern "C" int link_elk_out_ln_backward(const float *g_out, const float *A, const float *fin,
-                                        const int32_t *vox_sorted, const int32_t *pos_blk, const float *w_pos,
-                                        const float *alpha, const float *ln_w, const int32_t *hdr,
-                                        const link_elk_desc_t *desc, int64_t n, float *g_new, float *partials,
-                                        void *stream) {
-  if (check_desc(desc) != LINK_OK || n < 0 || (desc->c & 3) != 0) return LINK_ERR_ARG;
-  if (n == 0) return LINK_OK;
-  if (!g_out || !A || !vox_sorted || !pos_blk || !w_pos || !ln_w || !hdr || !g_new || !partials) return LINK_ERR_ARG;
-  if (desc->op == LINK_OP_COSX && !fin) return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  hipStream_t st = S(stream);
-  const int wgs = link_elk_mid_partial_rows();
-  switch (lanes_per_row(desc->c)) {
-    case 1: case 2: case 4: launch_out_ln_bwd<4>(*desc, wgs, st, g_out, A, fin, v4, pos_blk, w_pos, alpha, ln_w, hdr, g_new, partials); break;
-    case 8: launch_out_ln_bwd<8>(*desc, wgs, st, g_out, A, fin, v4, pos_blk, w_pos, alpha, ln_w, hdr, g_new, partials); break;
-    case 16: launch_out_ln_bwd<16>(*desc, wgs, st, g_out, A, fin, v4, pos_blk, w_pos, alpha, ln_w, hdr, g_new, partials); break;
-    case 32: launch_out_ln_bwd<32>(*desc, wgs, st, g_out, A, fin, v4, pos_blk, w_pos, alpha, ln_w, hdr, g_new, partials); break;
-    default: launch_out_ln_bwd<64>(*desc, wgs, st, g_out, A, fin, v4, pos_blk, w_pos, alpha, ln_w, hdr, g_new, partials); break;
-  }
-  return check_launch("link_elk_out_ln_backward");
-}
-
-// ---------------------------------------------------------------------------------------------
-// The block's tail for training (linkunet.py:183 / ts_elk.py:228): y = relu(addend + LayerNorm(x)),
-// forward and backward, one 16-byte-per-lane group per row (persistent grid).  Inference fuses this
-// tail into the convolution kernel instead (conv.hip, row N2).
-// ---------------------------------------------------------------------------------------------
-// IO (row_io.h): type of the x rows (the local_mix output; link_ln_add_relu_*_io); addend, y and g_y stay fp32.
-template <int LPR, int IO = LINK_IO_F32>
-__global__ void __launch_bounds__(256) k_ln_add_relu_fwd_g(const void *__restrict__ x,
-                                                           const float *__restrict__ addend,
-                                                           const float *__restrict__ ln_w,
-                                                           const float *__restrict__ ln_b, int64_t n, int c,
-                                                           float eps, float *__restrict__ y) {
-  constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & (LPR - 1), ch0 = 4 * li;
-  const bool act = ch0 < c;
-  const int cofs = act ? ch0 : 0;
-  const float inv_c = 1.0f / (float)c;
-  const float4 w4 = *reinterpret_cast<const float4 *>(&ln_w[cofs]), b4 = *reinterpret_cast<const float4 *>(&ln_b[cofs]);
-  const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
-  for (int64_t i = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; i < n; i += ngroups) {
-    float4 v = row_ld4<IO>(x, i * c + cofs);
-    const float4 a = *reinterpret_cast<const float4 *>(&addend[i * c + cofs]);
-    if (!act) v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float mean = grp_sum<LPR>((v.x + v.y) + (v.z + v.w)) * inv_c;
-    const float dx = act ? v.x - mean : 0.f, dy = act ? v.y - mean : 0.f, dz = act ? v.z - mean : 0.f, dw = act ? v.w - mean : 0.f;
-    const float rstd = 1.0f / sqrtf(grp_sum<LPR>((dx * dx + dy * dy) + (dz * dz + dw * dw)) * inv_c + eps);
-    if (act) {
-      float4 o;
-      o.x = fmaxf(a.x + (dx * rstd * w4.x + b4.x), 0.f);
-      o.y = fmaxf(a.y + (dy * rstd * w4.y + b4.y), 0.f);
-      o.z = fmaxf(a.z + (dz * rstd * w4.z + b4.z), 0.f);
-      o.w = fmaxf(a.w + (dw * rstd * w4.w + b4.w), 0.f);
-      *reinterpret_cast<float4 *>(&y[i * c + ch0]) = o;
-    }
-  }
-}
-
-template <int LPR, int IO = LINK_IO_F32>
-__global__ void __launch_bounds__(256) k_ln_add_relu_bwd_g(const float *__restrict__ g_y,
-                                                           const float *__restrict__ y,
-                                                           const void *__restrict__ x,
-                                                           const float *__restrict__ ln_w, int64_t n, int c,
-                                                           float eps, float *__restrict__ g_addend,
-                                                           void *__restrict__ g_x, float *__restrict__ partials) {
-  constexpr int G = 64 / LPR;
-  __shared__ float red[4][8][LPR];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & (LPR - 1), ch0 = 4 * li;
-  const bool act = ch0 < c;
-  const int cofs = act ? ch0 : 0;
-  const float inv_c = 1.0f / (float)c;
-  const float4 w4 = *reinterpret_cast<const float4 *>(&ln_w[cofs]);
-  const float gw[4] = {w4.x, w4.y, w4.z, w4.w};
-  float aw[4] = {0.f, 0.f, 0.f, 0.f}, ab[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t ngroups = (int64_t)gridDim.x * 4 * G;
-  for (int64_t i = ((int64_t)blockIdx.x * 4 + wave) * G + lane / LPR; i < n; i += ngroups) {
-    const float4 v4 = row_ld4<IO>(x, i * c + cofs);
-    const float4 y4 = *reinterpret_cast<const float4 *>(&y[i * c + cofs]);
-    const float4 g4 = *reinterpret_cast<const float4 *>(&g_y[i * c + cofs]);
-    const float xv[4] = {v4.x, v4.y, v4.z, v4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
-    float sm = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) sm += act ? xv[e] : 0.f;
-    const float mean = grp_sum<LPR>(sm) * inv_c;
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) { const float d = act ? xv[e] - mean : 0.f; q += d * d; }
-    const float rstd = 1.0f / sqrtf(grp_sum<LPR>(q) * inv_c + eps);
-    float g[4], xh[4], gx[4], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      g[e] = (act && yv[e] > 0.f) ? gv[e] : 0.f;              // ReLU mask from the saved output
-      xh[e] = act ? (xv[e] - mean) * rstd : 0.f;
-      gx[e] = g[e] * gw[e];
-      s1 += gx[e];
-      s2 = fmaf(gx[e], xh[e], s2);
-      aw[e] = fmaf(g[e], xh[e], aw[e]);
-      ab[e] += g[e];
-    }
-    const float m1 = grp_sum<LPR>(s1) * inv_c, m2 = grp_sum<LPR>(s2) * inv_c;
-    if (act) {
-      *reinterpret_cast<float4 *>(&g_addend[i * c + ch0]) = make_float4(g[0], g[1], g[2], g[3]);
-      row_st4<IO>(g_x, i * c + ch0,
-                  make_float4(rstd * (gx[0] - m1 - xh[0] * m2), rstd * (gx[1] - m1 - xh[1] * m2),
-                              rstd * (gx[2] - m1 - xh[2] * m2), rstd * (gx[3] - m1 - xh[3] * m2)));
-    }
-  }
-#pragma unroll
-  for (int o = LPR; o < 64; o <<= 1)
-#pragma unroll
-    for (int e = 0; e < 4; e++) { aw[e] += __shfl_xor(aw[e], o, 64); ab[e] += __shfl_xor(ab[e], o, 64); }
-  if (lane < LPR)
-#pragma unroll
-    for (int e = 0; e < 4; e++) { red[wave][e][li] = aw[e]; red[wave][4 + e][li] = ab[e]; }
-  __syncthreads();
-  if (wave == 0 && lane < LPR && act) {
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      float4 o;
-      o.x = (red[0][q * 4 + 0][li] + red[1][q * 4 + 0][li]) + (red[2][q * 4 + 0][li] + red[3][q * 4 + 0][li]);
-      o.y = (red[0][q * 4 + 1][li] + red[1][q * 4 + 1][li]) + (red[2][q * 4 + 1][li] + red[3][q * 4 + 1][li]);
-      o.z = (red[0][q * 4 + 2][li] + red[1][q * 4 + 2][li]) + (red[2][q * 4 + 2][li] + red[3][q * 4 + 2][li]);
-      o.w = (red[0][q * 4 + 3][li] + red[1][q * 4 + 3][li]) + (red[2][q * 4 + 3][li] + red[3][q * 4 + 3][li]);
-      *reinterpret_cast<float4 *>(&partials[((int64_t)blockIdx.x * 2 + q) * c + ch0]) = o;
-    }
-  }
-}
-
-extern "C" int32_t link_elk_mid_partial_rows(void);
-
-template <int IO>
-static int ln_add_relu_forward(const void *x, const float *addend, const float *ln_w, const float *ln_b, int64_t n, int32_t c,
-                               float eps, float *y, void *stream) {
-  if (n < 0 || c <= 0 || (c & 3) != 0 || c > 256) return LINK_ERR_ARG;
-  if (n == 0) return LINK_OK;
-  if (!x || !addend || !ln_w || !ln_b || !y) return LINK_ERR_ARG;
-  dim3 grid(1024), block(256);
-  hipStream_t st = S(stream);
-  switch (lanes_per_row(c)) {
-    case 1: case 2: case 4: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<4, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 8: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<8, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 16: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<16, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    case 32: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<32, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-    default: hipLaunchKernelGGL((k_ln_add_relu_fwd_g<64, IO>), grid, block, 0, st, x, addend, ln_w, ln_b, n, (int)c, eps, y); break;
-  }
-  return check_launch("link_ln_add_relu_forward");
-}
-
-template <int IO>
-static int ln_add_relu_backward(const float *g_y, const float *y, const void *x, const float *ln_w, int64_t n, int32_t c,
-                                float eps, float *g_addend, void *g_x, float *partials, void *stream) {
-  if (n < 0 || c <= 0 || (c & 3) != 0 || c > 256) return LINK_ERR_ARG;
-  if (!partials) return LINK_ERR_ARG;
-  if (n > 0 && (!g_y || !y || !x || !ln_w || !g_addend || !g_x)) return LINK_ERR_ARG;
-  dim3 grid(link_elk_mid_partial_rows()), block(256);
-  hipStream_t st = S(stream);
-  switch (lanes_per_row(c)) {
-    case 1: case 2: case 4: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<4, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 8: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<8, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 16: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<16, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    case 32: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<32, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-    default: hipLaunchKernelGGL((k_ln_add_relu_bwd_g<64, IO>), grid, block, 0, st, g_y, y, x, ln_w, n, (int)c, eps, g_addend, g_x, partials); break;
-  }
-  return check_launch("link_ln_add_relu_backward");
-}
-
-extern "C" int link_ln_add_relu_forward(const float *x, const float *addend, const float *ln_w,
-                                        const float *ln_b, int64_t n, int32_t c, float eps, float *y,
-                                        void *stream) {
-  return ln_add_relu_forward<LINK_IO_F32>(x, addend, ln_w, ln_b, n, c, eps, y, stream);
-}
-
-extern "C" int link_ln_add_relu_backward(const float *g_y, const float *y, const float *x, const float *ln_w,
-                                         int64_t n, int32_t c, float eps, float *g_addend, float *g_x,
-                                         float *partials, void *stream) {
-  return ln_add_relu_backward<LINK_IO_F32>(g_y, y, x, ln_w, n, c, eps, g_addend, g_x, partials, stream);
-}
-
-// ---------------------------------------------------------------------------------------------
-// 16-bit rows for autocast training (io_dtype = LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16): the kernels above instantiated per
-// row type (row_io.h) -- feats / x read, g_feats / g_x written in io_dtype, everything else fp32 as in the fp32 entries.
-// ---------------------------------------------------------------------------------------------
-#define LINK_ROW_IO(CALL)                                              \
-  switch (io_dtype) {                                                  \
-    case LINK_IO_F32: return CALL(LINK_IO_F32);                        \
-    case LINK_IO_F16: return CALL(LINK_IO_F16);                        \
-    case LINK_IO_BF16: return CALL(LINK_IO_BF16);                      \
-    default: return LINK_ERR_ARG;                                      \
-  }
-
-template <int IO>
-static int premix_ln_io(const void *feats, const float *w_pre, const float *ln_w, const float *ln_b, int64_t n, int32_t c,
-                        float eps, float *fin, hipStream_t st) {
-  switch (c) {
-    case 16: return launch_premix_tlp<16, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 32: return launch_premix_tlp<32, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 48: return launch_premix_tlp<48, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 64: return launch_premix_tlp<64, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 80: return launch_premix_tlp<80, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 96: return launch_premix_tlp<96, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    case 112: return launch_premix_tlp<112, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-    default: return launch_premix_tlp<128, IO>(feats, w_pre, ln_w, ln_b, n, eps, fin, st);
-  }
-}
-
-extern "C" int link_premix_ln_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w, const float *ln_b,
-                                 int64_t n, int32_t c, float eps, float *fin, void *stream) {
-  if (!row_io_ok(io_dtype)) return LINK_ERR_ARG;
-  if (io_dtype == LINK_IO_F32) return link_premix_ln(reinterpret_cast<const float *>(feats), w_pre, ln_w, ln_b, n, c, eps, fin, stream);
-  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;     // 16-bit rows: the MFMA widths only
-  if (n == 0) return LINK_OK;
-  if (!feats || !w_pre || !ln_w || !ln_b || !fin) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  if (io_dtype == LINK_IO_F16) return premix_ln_io<LINK_IO_F16>(feats, w_pre, ln_w, ln_b, n, c, eps, fin, st);
-  return premix_ln_io<LINK_IO_BF16>(feats, w_pre, ln_w, ln_b, n, c, eps, fin, st);
-}
-
-template <int IO>
-static int premix_ln_backward_io(const void *feats, const float *w_pre, const float *ln_w, const float *g_fin, int64_t n, int32_t c,
-                                 float eps, float *g_pre, void *g_feats, float *partials, hipStream_t st) {
-  const int wgs = link_elk_mid_partial_rows();
-  switch (c) {
-    case 16: return launch_premix_bwd<16, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 32: return launch_premix_bwd<32, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 48: return launch_premix_bwd<48, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 64: return launch_premix_bwd<64, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 80: return launch_premix_bwd<80, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 96: return launch_premix_bwd<96, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    case 112: return launch_premix_bwd<112, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-    default: return launch_premix_bwd<128, IO>(feats, w_pre, ln_w, g_fin, n, eps, g_pre, g_feats, partials, wgs, st);
-  }
-}
-
-extern "C" int link_premix_ln_backward_io(const void *feats, int32_t io_dtype, const float *w_pre, const float *ln_w,
-                                          const float *g_fin, int64_t n, int32_t c, float eps, float *g_pre, void *g_feats,
-                                          float *partials, void *stream) {
-  if (!row_io_ok(io_dtype)) return LINK_ERR_ARG;
-  if (n < 0 || c <= 0 || (c & 15) != 0 || c > 128) return LINK_ERR_ARG;
-  if (n == 0) return LINK_OK;
-  if (!feats || !w_pre || !ln_w || !g_fin || !g_pre || !g_feats || !partials) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-#define LINK_C(IO) premix_ln_backward_io<IO>(feats, w_pre, ln_w, g_fin, n, c, eps, g_pre, g_feats, partials, st)
-  LINK_ROW_IO(LINK_C)
-#undef LINK_C
-}
-
-extern "C" int link_ln_add_relu_forward_io(const void *x, int32_t io_dtype, const float *addend, const float *ln_w,
-                                           const float *ln_b, int64_t n, int32_t c, float eps, float *y, void *stream) {
-#define LINK_C(IO) ln_add_relu_forward<IO>(x, addend, ln_w, ln_b, n, c, eps, y, stream)
-  LINK_ROW_IO(LINK_C)
-#undef LINK_C
-}
-
-extern "C" int link_ln_add_relu_backward_io(const float *g_y, const float *y, const void *x, int32_t io_dtype, const float *ln_w,
-                                            int64_t n, int32_t c, float eps, float *g_addend, void *g_x, float *partials,
-                                            void *stream) {
-#define LINK_C(IO) ln_add_relu_backward<IO>(g_y, y, x, ln_w, n, c, eps, g_addend, g_x, partials, stream)
-  LINK_ROW_IO(LINK_C)
-#undef LINK_C
-}
-#undef LINK_ROW_IO
-
-// Column sums of up to three per-workgroup partial arrays [rows, cols_k] in one launch, fixed order
-// (row lanes ascending, then a fixed LDS tree): the deterministic tail of every parameter gradient.
-__global__ void __launch_bounds__(256) k_sum_partials(const float *__restrict__ p0, int c0,
-                                                      const float *__restrict__ p1, int c1,
-                                                      const float *__restrict__ p2, int c2, int64_t rows,
-                                                      float *__restrict__ out) {
-  __shared__ float red[32][8];
-  const int col = blockIdx.x * 8 + (threadIdx.x & 7), rl = threadIdx.x >> 3;
-  const int total = c0 + c1 + c2;
-  const float *src = nullptr;
-  int stride = 0, off = 0;
-  if (col < c0) { src = p0; stride = c0; off = col; }
-  else if (col < c0 + c1) { src = p1; stride = c1; off = col - c0; }
-  else if (col < total) { src = p2; stride = c2; off = col - c0 - c1; }
-  float acc = 0.f;
-  if (src)
-    for (int64_t r = rl; r < rows; r += 32) acc += src[r * stride + off];
-  red[rl][threadIdx.x & 7] = acc;
-  __syncthreads();
-  for (int h = 16; h >= 1; h >>= 1) {
-    if (rl < h) red[rl][threadIdx.x & 7] += red[rl + h][threadIdx.x & 7];
-    __syncthreads();
-  }
-  if (rl == 0 && col < total) out[col] = red[0][threadIdx.x & 7];
-}
-
-extern "C" int link_sum_partials(const float *p0, int32_t cols0, const float *p1, int32_t cols1,
-                                 const float *p2, int32_t cols2, int64_t rows, float *out, void *stream) {
-  if (cols0 < 0 || cols1 < 0 || cols2 < 0 || rows < 0 || !out) return LINK_ERR_ARG;
-  if ((cols0 && !p0) || (cols1 && !p1) || (cols2 && !p2)) return LINK_ERR_ARG;
-  const int total = cols0 + cols1 + cols2;
-  if (total == 0) return LINK_OK;
-  hipLaunchKernelGGL(k_sum_partials, dim3((total + 7) / 8), dim3(256), 0, S(stream), p0, (int)cols0, p1, (int)cols1,
-                     p2, (int)cols2, rows, out);
-  return check_launch("link_sum_partials");
-}
-
-static int train_args_ok(const link_elk_desc_t *desc, const link_grid_t *grid, int64_t n, int64_t m_cap) {
-  if (check_desc(desc) != LINK_OK || !grid || n < 0 || m_cap < 0) return LINK_ERR_ARG;
-  if ((desc->c & 3) != 0 || desc->r > 3) return LINK_ERR_ARG;      // group kernels only; callers fall back
-  return LINK_OK;
-}
-
-extern "C" int link_elk_mid_forward(const float *fin, const int32_t *vox_sorted, const int32_t *pos_blk,
-                                    const int32_t *blk_start, const int32_t *blk_coords,
-                                    const int32_t *cell_blk, const link_grid_t *grid, const int32_t *hdr,
-                                    const float *w_pos, const float *alpha, const link_elk_desc_t *desc,
-                                    const float *ln_w, const float *ln_b, int64_t n, int64_t m_cap,
-                                    float *S_, float *A, float *den, float *out, void *stream) {
-  int rc = train_args_ok(desc, grid, n, m_cap);
-  if (rc != LINK_OK) return rc;
-  if (n == 0 || m_cap == 0) return LINK_OK;
-  if (!fin || !vox_sorted || !pos_blk || !blk_start || !blk_coords || !cell_blk || !hdr || !w_pos || !S_ || !A ||
-      !den || !out)
-    return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  if (!modsum_group_path(desc, S(stream), fin, v4, w_pos, alpha, blk_start, hdr, S_, m_cap)) return LINK_ERR_ARG;
-  rc = check_launch("link_elk_mid_forward");
-  if (rc != LINK_OK) return rc;
-  rc = block_gather_impl(S_, blk_coords, cell_blk, grid, hdr, desc, m_cap, A, 0, den, stream);
-  if (rc != LINK_OK) return rc;
-  if ((ln_w == nullptr) != (ln_b == nullptr)) return LINK_ERR_ARG;
-  return voxel_demod_impl(A, fin, vox_sorted, pos_blk, w_pos, alpha, ln_w, ln_b, hdr, desc, n, out, stream);
-}
-
-extern "C" int link_elk_mid_backward(const float *g_out, const float *fin, const float *A, const float *den,
-                                     const int32_t *vox_sorted, const int32_t *pos_blk,
-                                     const int32_t *blk_start, const int32_t *blk_coords,
-                                     const int32_t *cell_blk, const link_grid_t *grid, const int32_t *hdr,
-                                     const float *w_pos, const float *alpha, const link_elk_desc_t *desc,
-                                     int64_t n, int64_t m_cap, float *S_, float *gS, float *g_fin,
-                                     float *partials, void *stream) {
-  int rc = train_args_ok(desc, grid, n, m_cap);
-  if (rc != LINK_OK) return rc;
-  if (n == 0 || m_cap == 0) return LINK_OK;
-  if (!g_out || !fin || !A || !den || !vox_sorted || !pos_blk || !blk_start || !blk_coords || !cell_blk || !hdr ||
-      !w_pos || !S_ || !gS || !g_fin || !partials)
-    return LINK_ERR_ARG;
-  const int4 *v4 = reinterpret_cast<const int4 *>(vox_sorted);
-  hipStream_t st = S(stream);
-  const int bop = desc->op == LINK_OP_COS ? LINK_OP_COS : (desc->op == LINK_OP_SIN ? LINK_OPI_SIN_BWD : LINK_OPI_COSX_BWD);
-  if (!modsum_group_path(desc, st, g_out, v4, w_pos, alpha, blk_start, hdr, S_, m_cap, bop, den)) return LINK_ERR_ARG;
-  rc = check_launch("link_elk_mid_backward");
-  if (rc != LINK_OK) return rc;
-  rc = block_gather_impl(S_, blk_coords, cell_blk, grid, hdr, desc, m_cap, gS, 1 | 2, nullptr, stream);
-  if (rc != LINK_OK) return rc;
-  const int wgs = link_elk_mid_partial_rows();
-  switch (lanes_per_row(desc->c)) {
-    case 1: case 2: case 4: launch_voxel_bwd<4>(*desc, wgs, st, gS, A, fin, g_out, v4, pos_blk, w_pos, alpha, hdr, g_fin, partials); break;
-    case 8: launch_voxel_bwd<8>(*desc, wgs, st, gS, A, fin, g_out, v4, pos_blk, w_pos, alpha, hdr, g_fin, partials); break;
-    case 16: launch_voxel_bwd<16>(*desc, wgs, st, gS, A, fin, g_out, v4, pos_blk, w_pos, alpha, hdr, g_fin, partials); break;
-    case 32: launch_voxel_bwd<32>(*desc, wgs, st, gS, A, fin, g_out, v4, pos_blk, w_pos, alpha, hdr, g_fin, partials); break;
-    default: launch_voxel_bwd<64>(*desc, wgs, st, gS, A, fin, g_out, v4, pos_blk, w_pos, alpha, hdr, g_fin, partials); break;
-  }
-  return check_launch("link_elk_mid_backward");
 }
 
 // ---------------------------------------------------------------------------------------------
