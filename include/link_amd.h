@@ -607,6 +607,37 @@ int link_conv_site_table(const int32_t *indices, int64_t n, const int32_t *in_sh
 int link_conv_gather_table(const int32_t *out_indices, int64_t m, const int32_t *kernel, const int32_t *stride,
                            const int32_t *padding, const int32_t *in_shape, int32_t batch, const int32_t *site_table,
                            int32_t *table, void *stream);
+/* General geometries: the kernel map of a convolution with ANY per-axis kernel size (1..7) and stride, as the reference's
+ * conv3d builds it (nn/functional/conv.py:103-122).  Coordinates i32[.,4] = (x, y, z, b); per-axis arrays are i32[3] on the host.
+ *
+ * link_kmap_out_candidates -- the candidate rule of spdownsample (nn/functional/downsample.py:30-44, taken when some axis has
+ *   1 < stride != kernel): an output site is every input + offset (offsets per axis arange(-k//2+1, k//2+1) * tensor_stride,
+ *   nn/utils/kernel.py:20) whose coordinates are multiples of stride * tensor_stride and not below lo[0..2], the per-axis
+ *   minimum of the inputs (lo[3] = the smallest batch index); there is no upper filter, as in the reference.  One thread per
+ *   (input, combination of one on-lattice tap per axis): cand i32[n * link_kmap_candidate_count, 4] receives the sites in
+ *   LATTICE units, rows (b, x / ss, y / ss, z / ss) with ss = stride * tensor_stride -- the row form link_index_cells sorts
+ *   into the (batch, x, y, z) order of downsample.py:46-50 -- and rows (lo[3] - 1, 0, 0, 0), which every grid over the inputs'
+ *   batch range drops, where a combination gives no site (an input that is not a multiple of tensor_stride gives none, as in
+ *   the reference: (c + j * ts) % (s * ts) == 0 needs c % ts == 0).  lo must be the EXACT per-axis minimum, not a lower bound.  link_kmap_candidate_count = prod ceil(kernel / stride), -1 for
+ *   arguments the builder does not take.  (link_conv_out_candidates above is spconv's rule -- padding, an output shape --
+ *   and a different relation.)
+ * link_kmap_box_table -- table i32[m, K], K = kx * ky * kz: table[j, k] = the input row at rows[j] + offset_k, offsets
+ *   (tap_x * step_x, tap_y * step_y, tap_z * step_z) in get_kernel_offsets order (kernel.py:24-30: odd K x fastest and z
+ *   outermost, even K z fastest and x outermost), -1 where no input lies; step = the input's tensor stride per axis
+ *   (conv.py:105-107: the dilation is not applied).  cell_tab: link_cell_table_build over the input rows on `grid` (block
+ *   edge 1).  Replaces sphash(out, offsets) -> sphashquery (conv.py:108-113) for the box; link_neighbor_map is the cubic,
+ *   one-step case and stays as it is.  m * K < 2^31.
+ * link_kmap_transpose -- the opposite direction: back i32[n_in, K] with back[i, k] = j <=> table[j, k] = i, -1 elsewhere
+ *   (out + offset_k = in fixes out, for any geometry): the table of the transposed convolution and of the input gradient,
+ *   which the reference reads off the same pair list with the two columns swapped (conv.py:114-118, convolution_cuda.cu:
+ *   `transpose`).  A fill with -1 and one launch; entries of `table` outside [0, n_in) are ignored; among duplicate output
+ *   rows the smallest j wins (deterministic). */
+int32_t link_kmap_candidate_count(const int32_t *kernel, const int32_t *stride);
+int link_kmap_out_candidates(const int32_t *coords, int64_t n, const int32_t *kernel, const int32_t *stride,
+                             const int32_t *tensor_stride, const int32_t *lo, int32_t *cand, void *stream);
+int link_kmap_box_table(const int32_t *rows, int64_t m, const int32_t *cell_tab, const link_grid_t *grid,
+                        const int32_t *kernel, const int32_t *step, int32_t *table, void *stream);
+int link_kmap_transpose(const int32_t *table, int64_t m, int32_t kvol, int64_t n_in, int32_t *back, void *stream);
 /* Building the pair plan from a per-output neighbour table nbr i32[n, kvol] (-1 absent), kvol <= 64 -- the device
  * half of what nn/functional/conv.py:109-122 does with nonzero / sum on the host side.  G = ceil(n / 256) workgroups:
  *   link_pair_plan_count   wg_counts i32[G, kvol + 1]: per workgroup, pairs of every offset, and (last column) rows

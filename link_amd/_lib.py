@@ -184,6 +184,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "link_conv_out_candidate_count": (c_int32, [c_void_p, c_void_p]),
     "link_conv_out_candidates": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # kernel maps of any per-axis kernel size / stride (csrc/kmap.hip)
+    "link_kmap_candidate_count": (c_int32, [c_void_p, c_void_p]),
+    "link_kmap_out_candidates": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "link_kmap_box_table": (c_int, [c_void_p, c_int64, c_void_p, POINTER(LinkGrid), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "link_kmap_transpose": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p]),
     "link_conv_pairs_gemm_io": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "link_conv_pairs_sum_io": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_float, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),

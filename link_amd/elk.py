@@ -36,7 +36,7 @@ import torch.nn.functional as TF
 from . import _lib as L
 from .aggregate import _AuxToVoxel, _BlockMean, link_index_of
 from .functional import sphash, sphashquery
-from .index import BlockIndex, GridTooLarge, foreign_neighbor_map
+from .index import BlockIndex, GridTooLarge, box_neighbor_map, foreign_neighbor_map, strided_out_coords, transpose_table
 from .tensor import SparseTensor
 from .utils import get_kernel_offsets, make_ntuple
 
@@ -962,8 +962,8 @@ def elk_core_train(feats, coords, index, w_pre, pre_ln_w, pre_ln_b, w_pos, alpha
 # local 3^3 sparse convolution (row N1 of SURVEY.md section 8f, minimal form)
 # ------------------------------------------------------------------------------------------------
 class _StridedMap:
-    """Kernel map of a kernel-2 stride-2 convolution: coarse coordinates + the per-output table of the
-    down direction [N_coarse, 8] and of the transposed direction [N_fine, 8] (one parent per fine voxel)."""
+    """Kernel map of a convolution between two site sets (any kernel / stride; kernel 2 / stride 2 in the LinK networks):
+    output coordinates + the per-output table of the plain direction [N_out, K] and of the transposed direction [N_in, K]."""
 
     def __init__(self, out_coords, nbr_down, nbr_up):
         self.out_coords, self.nbr_down, self._nbr_up, self._n_in = out_coords, nbr_down, nbr_up, None
@@ -973,11 +973,7 @@ class _StridedMap:
         """[N_fine, K] with the one coarse row that reads fine row i through offset k (-1 elsewhere): the table of the
         transposed convolution and of the input gradient.  Built on first use (inference encoders never need it)."""
         if self._nbr_up is None:
-            down = self.nbr_down
-            jj, kk = torch.nonzero(down >= 0, as_tuple=True)
-            up = torch.full((self._n_in, down.shape[1]), -1, dtype=torch.int32, device=down.device)
-            up[down[jj, kk].long(), kk] = jj.int()
-            self._nbr_up = up
+            self._nbr_up = transpose_table(self.nbr_down, self._n_in)   # link_kmap_transpose: no nonzero round trip
         return self._nbr_up
 
 
@@ -990,6 +986,21 @@ def mark_unique(cmaps: dict, coords: torch.Tensor) -> None:
     cmaps[("link_unique", coords.data_ptr(), coords.shape[0])] = True
 
 
+def _bounds_of(x: SparseTensor):
+    """Inclusive bounding box of x's coordinates: the one bounds pass per coordinate set the block index shares (cmaps);
+    bounds that came from the caller's metadata are measured again (a cell table is addressed with them).  Every box cached
+    under "link_bounds" is TIGHT: its lower corner is the per-axis minimum the candidate rule of spdownsample filters with."""
+    bkey = ("link_bounds", x.C.data_ptr(), x.C.shape[0])
+    bounds = x.cmaps.get(bkey)
+    if bounds is None or x.cmaps.get(("link_bounds_unchecked", x.C.data_ptr(), x.C.shape[0])):
+        from .index import coords_bounds
+        fresh = coords_bounds(x.C.contiguous())
+        if bounds is None and x.C.is_contiguous():
+            x.cmaps[bkey] = fresh
+        bounds = fresh
+    return bounds
+
+
 def neighbor_table_of(x: SparseTensor, kernel_size):
     """Per-output neighbour table of a stride-1 convolution over x's voxels: (int32[N, K], spatial tile order or
     None), cached on the tensor's kmaps (every convolution with this kernel size over these coordinates shares it)."""
@@ -998,18 +1009,14 @@ def neighbor_table_of(x: SparseTensor, kernel_size):
     if nbr is None:
         # neighbour of voxel i at coords_i + offset*tensor_stride (conv.py:105-113: stride=input.stride)
         ts = int(x.s[0])
-        bkey = ("link_bounds", x.C.data_ptr(), x.C.shape[0])
-        bounds = x.cmaps.get(bkey)
-        if bounds is None or x.cmaps.get(("link_bounds_unchecked", x.C.data_ptr(), x.C.shape[0])):
-            # one bounding-box pass per coordinate set, shared with the block index; bounds that came from the
-            # caller's metadata are not trusted here (the cell table is addressed with them)
-            from .index import coords_bounds
-            fresh = coords_bounds(x.C.contiguous())
-            if bounds is None and x.C.is_contiguous():
-                x.cmaps[bkey] = fresh
-            bounds = fresh
+        bounds = _bounds_of(x)
+        cubic = len(set(kernel_size)) == 1 and len(set(x.s)) == 1
+        ts = ts if cubic else max(int(v) for v in x.s)      # (the tile order below: the largest per-axis stride)
         try:
-            nbr = foreign_neighbor_map(x.C, kernel_size[0], step=ts, bounds=bounds)
+            if cubic:
+                nbr = foreign_neighbor_map(x.C, kernel_size[0], step=ts, bounds=bounds)
+            else:                                           # per-axis extents / per-axis tensor stride: the box builder
+                nbr = box_neighbor_map(x.C, kernel_size, x.s, bounds=bounds)
         except GridTooLarge:
             offs = get_kernel_offsets(kernel_size, stride=x.s, device=x.F.device)
             nbr = sphashquery(sphash(x.C, offs), sphash(x.C)).t().contiguous().int()
@@ -1053,14 +1060,22 @@ class _TileOrder:
         return self._perm.data_ptr() if self._perm is not None else None
 
 
+def _check_geometry(kernel_size, stride) -> None:
+    if not all(int(k) == k and 1 <= k <= 7 for k in kernel_size) or not all(int(s) == s and s >= 1 for s in stride):
+        raise ValueError(f"sparse convolution: per-axis kernel sizes 1..7 and strides >= 1, got {kernel_size} / {stride}")
+
+
 class Conv3d(nn.Module):
     """Sparse convolution with the reference's parameter layout (`kernel` [K, Cin, Cout], optional `bias`;
-    torchsparse/nn/modules/conv.py:15-72; init U(+-1/sqrt(Cin*K)), or Cout*K when transposed) for the forms
-    the LinK networks use (linkunet.py:40-92,109): odd cubic kernels at stride 1 (submanifold), and
-    kernel 2 / stride 2 down-sampling and transposed up-sampling.  Kernel maps are per-output neighbour
-    tables from the dense cell table (HIP) -- the same relation the reference builds with sphash ->
-    sphashquery -> nonzero (nn/functional/conv.py:103-122) -- cached on the tensor's kmaps under the
-    reference's key; contraction by the output-stationary MFMA kernel (include/link_amd.h section D)."""
+    torchsparse/nn/modules/conv.py:15-72; init U(+-1/sqrt(Cin*K)), or Cout*K when transposed) for any per-axis
+    kernel size (1..7) and stride, plain or transposed (nn/functional/conv.py:83-147).  The forms the LinK networks use
+    (linkunet.py:40-92,109) -- odd cubic kernels at stride 1, kernel 2 / stride 2 down and transposed -- keep their own map
+    builders; every other geometry takes the box builder (include/link_amd.h, "general geometries").  Kernel maps are
+    per-output neighbour tables from the dense cell table (HIP) -- the same relation the reference builds with sphash ->
+    sphashquery -> nonzero (nn/functional/conv.py:103-122) -- cached on the tensor's kmaps under the reference's key;
+    contraction by the output-stationary MFMA kernel or the pair-list kernels (include/link_amd.h section D).  A transposed
+    layer reads the map a matching plain layer left on kmaps (KeyError without one, as in the reference); `dilation` is
+    part of that key and of nothing else, as in the reference (conv.py:105-107)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 3, stride: int = 1,
                  dilation: int = 1, bias: bool = False, transposed: bool = False) -> None:
@@ -1069,13 +1084,8 @@ class Conv3d(nn.Module):
         self.kernel_size = make_ntuple(kernel_size, 3)
         self.stride = make_ntuple(stride, 3)
         self.dilation, self.transposed = dilation, transposed
-        if len(set(self.kernel_size)) != 1 or len(set(self.stride)) != 1:
-            raise NotImplementedError("cubic kernels / isotropic strides only")
-        ks, st = self.kernel_size[0], self.stride[0]
-        if not ((st == 1 and ks % 2 == 1 and not transposed) or (st == 2 and ks == 2)):
-            raise NotImplementedError("link_amd.Conv3d implements odd kernels at stride 1 and kernel 2 / stride 2 "
-                                      "(down-sampling or transposed)")
-        self.kernel_volume = ks ** 3
+        _check_geometry(self.kernel_size, self.stride)
+        self.kernel_volume = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
         if self.kernel_volume > 1:
             self.kernel = nn.Parameter(torch.zeros(self.kernel_volume, in_channels, out_channels))
         else:
@@ -1100,17 +1110,13 @@ class Conv3d(nn.Module):
         (downsample.py:26-49), table[j,k] = input row at out_coords[j] + offset_k * ts."""
         key = (x.s, self.kernel_size, self.stride, self.dilation)
         km = x.kmaps.get(key)
+        if km is None and not (self.kernel_size == (2, 2, 2) and self.stride == (2, 2, 2) and len(set(x.s)) == 1):
+            km = x.kmaps[key] = self._general_map(x)
         if km is None:
             ts = int(x.s[0])
             ss = ts * self.stride[0]
             # unique rows in (batch, x, y, z) order through ONE linear key (a 1-D sort instead of a 4-column one)
-            bkey = ("link_bounds", x.C.data_ptr(), x.C.shape[0])
-            bounds = x.cmaps.get(bkey)
-            if bounds is None or x.cmaps.get(("link_bounds_unchecked", x.C.data_ptr(), x.C.shape[0])):
-                from .index import coords_bounds
-                bounds = coords_bounds(x.C.contiguous())
-                if x.C.is_contiguous() and bkey not in x.cmaps:
-                    x.cmaps[bkey] = bounds
+            bounds = _bounds_of(x)
             # sorted unique (batch, x', y', z') rows of the block coordinates through the dense cell grid (link_index_cells:
             # four launches and the one host round trip that sizes the output, instead of a 1-D key, torch.unique's device
             # sort with its own round trip, and the decode)
@@ -1153,6 +1159,61 @@ class Conv3d(nn.Module):
             x.kmaps[key] = km
         return km
 
+    def _general_map(self, x: SparseTensor) -> _StridedMap:
+        """The kernel map of any other strided geometry (per-axis kernel, stride and tensor stride): output coordinates by
+        spdownsample's rule (strided_out_coords: the candidate kernel or the floor, then link_index_cells), the table by the box
+        builder; beyond the dense-grid limit the Python spdownsample and the hash chain (conv.py:103-113 as written)."""
+        ks, st, ts = self.kernel_size, self.stride, tuple(int(v) for v in x.s)
+        bounds = _bounds_of(x)
+        try:
+            out_c, box = strided_out_coords(x.C, bounds, ks, st, ts)
+        except GridTooLarge:
+            out_c, box = _spdownsample_torch(x.C, st, ks, ts), None
+        mark_unique(x.cmaps, out_c)
+        if box is not None:                              # a TIGHT box only (the floor rule): a later candidate-rule layer reads its
+            x.cmaps.setdefault(("link_bounds", out_c.data_ptr(), out_c.shape[0]), box)    # lower corner as the inputs' minimum
+        try:
+            down = box_neighbor_map(out_c, ks, ts, table_rows=x.C, bounds=bounds)
+        except GridTooLarge:
+            offs = get_kernel_offsets(ks, stride=ts, device=x.C.device)
+            down = sphashquery(sphash(out_c, offs), sphash(x.C)).t().contiguous().int()
+        try:
+            down._link_subm = False
+        except AttributeError:
+            pass
+        km = _StridedMap(out_c, down, None)
+        km._n_in = x.C.shape[0]
+        return km
+
+    def _unit_map(self, x: SparseTensor, nbr: torch.Tensor) -> _StridedMap:
+        """A stride-1 table under the reference's key too (conv.py:103): where a transposed stride-1 layer looks it up."""
+        key = (x.s, self.kernel_size, self.stride, self.dilation)
+        km = x.kmaps.get(key)
+        if km is None or km.nbr_down is not nbr:
+            km = x.kmaps[key] = _StridedMap(x.C, nbr, None)
+            km._n_in = x.C.shape[0]
+        return km
+
+    def _route(self, x: SparseTensor, need_back: bool):
+        """(table, table of the opposite direction or None, tile order, submanifold, coordinates, tensor stride) of this layer
+        over x; table None = a plain matrix product on the rows (kernel 1 at stride 1)."""
+        unit = all(s == 1 for s in self.stride)
+        if unit and self.kernel_volume == 1:
+            return None, None, None, False, x.C, x.s
+        if not self.transposed:
+            if unit:
+                nbr, order = self._neighbor_table(x)
+                km = self._unit_map(x, nbr)
+                # a symmetric relation (w'[k] = w[K-1-k]^T gives the input gradient) only when all three extents are odd
+                subm = self.kernel_volume % 2 == 1
+                return nbr, (km.nbr_up if need_back and not subm else None), order, subm, x.C, x.s
+            km = self._strided_map(x)
+            return (km.nbr_down, km.nbr_up if need_back else None, None, False, km.out_coords,
+                    tuple(x.s[k] * self.stride[k] for k in range(3)))
+        stride = tuple(x.s[k] // self.stride[k] for k in range(3))
+        km = x.kmaps[(stride, self.kernel_size, self.stride, self.dilation)]   # the matching plain layer's map (KeyError: none ran)
+        return km.nbr_up, km.nbr_down, None, False, x.cmaps[stride], stride
+
     def forward(self, x: SparseTensor) -> SparseTensor:
         if x.F.is_cuda and torch.is_autocast_enabled("cuda"):
             # the reference's custom_fwd(cast_inputs=torch.half) (nn/functional/conv.py:19): rows, kernel and bias in fp16,
@@ -1163,22 +1224,14 @@ class Conv3d(nn.Module):
         return self._forward(x, x.F, self.bias)
 
     def _forward(self, x: SparseTensor, feats: torch.Tensor, bias: Optional[torch.Tensor], half: bool = False) -> SparseTensor:
-        if self.stride[0] == 1:
-            if self.kernel_volume == 1:
-                out = feats.matmul(self.kernel.half() if half else self.kernel)
-            else:
-                nbr, order = self._neighbor_table(x)
-                out = _SubmConv.apply(feats, self.kernel, nbr, order)
-            coords, stride = x.C, x.s
-        elif not self.transposed:
-            km = self._strided_map(x)
-            out = _GatherConv.apply(feats, self.kernel, km.nbr_down, km.nbr_up)
-            coords, stride = km.out_coords, tuple(x.s[k] * self.stride[k] for k in range(3))
+        table, back, order, subm, coords, stride = self._route(x, need_back=True)
+        kernel = self.kernel if self.kernel.ndim == 3 or table is None else self.kernel.unsqueeze(0)   # K = 1 off stride 1: [Cin, Cout]
+        if table is None:
+            out = feats.matmul(self.kernel.half() if half else self.kernel)
+        elif subm:
+            out = _SubmConv.apply(feats, kernel, table, order)
         else:
-            stride = tuple(x.s[k] // self.stride[k] for k in range(3))
-            km = x.kmaps[(stride, self.kernel_size, self.stride, self.dilation)]   # the matching down-conv's map
-            out = _GatherConv.apply(feats, self.kernel, km.nbr_up, km.nbr_down)
-            coords = x.cmaps[stride]
+            out = _GatherConv.apply(feats, kernel, table, back)
         if bias is not None:
             out = out + bias
         y = SparseTensor(out, coords, stride)
@@ -1191,23 +1244,13 @@ class Conv3d(nn.Module):
         BatchNorm (running statistics, folded to scale / shift together with this module's bias by the caller)
         and ReLU in its finish phase (linkunet.py:23-92: BasicConvolutionBlock / ResidualBlock / *_tail)."""
         feats = x.F
-        if self.stride[0] == 1:
-            coords, stride = x.C, x.s
-            table, order = (None, None) if self.kernel_volume == 1 else self._neighbor_table(x)
-        elif not self.transposed:
-            km = self._strided_map(x)
-            table, order = km.nbr_down, None
-            coords, stride = km.out_coords, tuple(x.s[k] * self.stride[k] for k in range(3))
-        else:
-            stride = tuple(x.s[k] // self.stride[k] for k in range(3))
-            km = x.kmaps[(stride, self.kernel_size, self.stride, self.dilation)]
-            table, order = km.nbr_up, None
-            coords = x.cmaps[stride]
+        table, _, order, _, coords, stride = self._route(x, need_back=False)
         if table is None:                               # 1x1x1: a dense GEMM on the rows
             out = torch.addcmul(shift, feats.float().matmul(self.kernel.detach()), scale)
             out = torch.relu_(out) if relu else out
         else:
-            out = subm_conv_ln_add_relu(feats, self.kernel, table, order, scale, shift, 0.0, None, relu=relu, affine=True)
+            kernel = self.kernel if self.kernel.ndim == 3 else self.kernel.unsqueeze(0)
+            out = subm_conv_ln_add_relu(feats, kernel, table, order, scale, shift, 0.0, None, relu=relu, affine=True)
         y = SparseTensor(out, coords, stride)
         y.cmaps, y.kmaps = x.cmaps, x.kmaps
         y.cmaps.setdefault(y.stride, y.coords)
@@ -1217,16 +1260,14 @@ class Conv3d(nn.Module):
 def conv3d(input: SparseTensor, weight: torch.Tensor, kernel_size, bias: Optional[torch.Tensor] = None, stride=1,
            dilation=1, transposed: bool = False) -> SparseTensor:
     """Functional form of the sparse convolution (torchsparse/nn/functional/conv.py:83-147: same arguments, same
-    kmaps / cmaps contract) on the kernels behind link_amd.Conv3d; forms as the module's (odd kernels at stride 1,
-    kernel 2 / stride 2 down and transposed)."""
+    kmaps / cmaps contract) on the kernels behind link_amd.Conv3d: any per-axis kernel size 1..7 and stride, plain or
+    transposed."""
     ks, st = make_ntuple(kernel_size, 3), make_ntuple(stride, 3)
     shell = Conv3d.__new__(Conv3d)                     # the module's forward with the caller's tensors as parameters
     nn.Module.__init__(shell)
     shell.kernel_size, shell.stride, shell.dilation, shell.transposed = ks, st, dilation, transposed
-    if len(set(ks)) != 1 or len(set(st)) != 1 or not ((st[0] == 1 and ks[0] % 2 == 1 and not transposed) or
-                                                      (st[0] == 2 and ks[0] == 2)):
-        raise NotImplementedError("link_amd conv3d: odd cubic kernels at stride 1, kernel 2 / stride 2 (down or transposed)")
-    shell.kernel_volume = ks[0] ** 3
+    _check_geometry(ks, st)
+    shell.kernel_volume = ks[0] * ks[1] * ks[2]
     shell.in_channels, shell.out_channels = weight.shape[-2], weight.shape[-1]
     shell.__dict__["kernel"], shell.__dict__["bias"] = weight, bias
     return Conv3d.forward(shell, input)
@@ -1238,6 +1279,21 @@ def spdownsample(coords: torch.Tensor, stride=2, kernel_size=2, tensor_stride=1)
     otherwise every position input + offset that lies on the coarse lattice (and not below the inputs' minimum)
     is an output.  Rows unique, ordered by (batch, x, y, z)."""
     stride, ks, ts = make_ntuple(stride, 3), make_ntuple(kernel_size, 3), make_ntuple(tensor_stride, 3)
+    if (coords.is_cuda and coords.dtype == torch.int32 and coords.shape[0] > 0 and all(1 <= k <= 7 for k in ks)
+            and not all(stride[k] in (1, ks[k]) for k in range(3))):
+        # the candidate rule on the device: the builder the strided convolutions use (one bounds pass, link_kmap_out_candidates,
+        # link_index_cells) instead of N x K x 3 temporaries and a four-column sort; same rows, same order (inputs that are
+        # not multiples of tensor_stride give no site on either path: (c + j * ts) % (s * ts) == 0 needs c % ts == 0)
+        from .index import coords_bounds
+        try:
+            return strided_out_coords(coords, coords_bounds(coords.contiguous()), ks, stride, ts)[0]
+        except GridTooLarge:
+            pass
+    return _spdownsample_torch(coords, stride, ks, ts)
+
+
+def _spdownsample_torch(coords: torch.Tensor, stride, ks, ts) -> torch.Tensor:
+    """spdownsample as the reference writes it, in torch: the path beyond the dense-grid limit (and of CPU tensors)."""
     ss = torch.tensor([stride[k] * ts[k] for k in range(3)], dtype=torch.int32, device=coords.device)
     if all(stride[k] in (1, ks[k]) for k in range(3)):
         c = coords.clone()

@@ -300,3 +300,123 @@ def foreign_neighbor_map(rows: torch.Tensor, r: int, transpose: bool = False, st
         ws.drop_cell_table()          # the 'all zero between calls' invariant no longer holds for this table
         raise
     return nbr
+
+
+# ------------------------------------------------------------------------------------------------
+# kernel maps of any per-axis kernel size / stride (include/link_amd.h section D, "general geometries")
+# ------------------------------------------------------------------------------------------------
+def _i3(v):
+    return (ctypes.c_int32 * 3)(*[int(a) for a in v])
+
+
+def box_neighbor_map(rows: torch.Tensor, kernel, step, table_rows: Optional[torch.Tensor] = None, bounds=None) -> torch.Tensor:
+    """foreign_neighbor_map for a BOX of offsets: int32[M, kx*ky*kz], entry [j, k] = the index in `table_rows` (default: the
+    rows themselves) of rows[j] + offset_k, offsets = per-axis taps (kernel 1..7 each) times the per-axis `step`, in
+    get_kernel_offsets order; -1 absent.  Cell table in the workspace, built and cleared around the one look-up launch."""
+    rows = rows.contiguous()
+    m, dev = rows.shape[0], rows.device
+    kvol = int(kernel[0]) * int(kernel[1]) * int(kernel[2])
+    if m * kvol >= 1 << 31:
+        raise GridTooLarge(f"table of {m} x {kvol} entries: beyond the builder's 2^31 (the callers' hash chain takes it)")
+    nbr = torch.empty((m, kvol), dtype=torch.int32, device=dev)
+    if m == 0:
+        return nbr
+    src = rows if table_rows is None else table_rows.contiguous()
+    if src.shape[0] == 0:
+        return nbr.fill_(-1)
+    lo, hi = bounds if bounds is not None else coords_bounds(src)
+    try:
+        grid = L.grid_from_bounds(lo, hi, 1)
+    except L.LinkAmdError as e:
+        raise GridTooLarge(str(e))
+    if grid.cells > MAX_CELLS:
+        raise GridTooLarge(f"dense block grid would need {grid.cells} cells")
+    ws = _workspace(dev)
+    table = ws.cell_table(grid.cells)
+    st = L.current_stream_handle()
+    try:
+        L.check(L.lib().link_cell_table_build(src.data_ptr(), src.shape[0], ctypes.byref(grid), table.data_ptr(), None,
+                                              st), "link_cell_table_build")
+        L.check(L.lib().link_kmap_box_table(rows.data_ptr(), m, table.data_ptr(), ctypes.byref(grid), _i3(kernel), _i3(step),
+                                            nbr.data_ptr(), st), "link_kmap_box_table")
+        L.check(L.lib().link_cell_table_clear(src.data_ptr(), src.shape[0], ctypes.byref(grid), table.data_ptr(), st),
+                "link_cell_table_clear")
+    except Exception:
+        ws.drop_cell_table()
+        raise
+    return nbr
+
+
+def transpose_table(table: torch.Tensor, n_in: int) -> torch.Tensor:
+    """back int32[n_in, K] with back[i, k] = j <=> table[j, k] = i, -1 elsewhere (link_kmap_transpose): the per-output table of
+    the opposite direction of a kernel map.  m * K and n_in * K below 2^31 (LinkAmdError beyond)."""
+    table = table.contiguous()
+    m, kvol = table.shape
+    back = torch.empty((n_in, kvol), dtype=torch.int32, device=table.device)
+    L.check(L.lib().link_kmap_transpose(table.data_ptr(), m, kvol, n_in, back.data_ptr(), L.current_stream_handle()),
+            "link_kmap_transpose")
+    return back
+
+
+_SMALL_I32: Dict = {}
+
+
+def _dev_i32(device, values) -> torch.Tensor:
+    """A few ints as a device tensor, cached per (device, values): one H2D copy per geometry, not per map."""
+    key = (device, tuple(int(v) for v in values))
+    t = _SMALL_I32.get(key)
+    if t is None:
+        if len(_SMALL_I32) > 256:
+            _SMALL_I32.clear()
+        t = _SMALL_I32[key] = torch.tensor(key[1], dtype=torch.int32, device=device)
+    return t
+
+
+def strided_out_coords(coords: torch.Tensor, bounds, kernel, stride, tensor_stride):
+    """Output coordinates of a strided convolution over int32 `coords`[n,4] with inclusive `bounds`, by the reference's rule
+    (nn/functional/downsample.py:11-51): every axis with stride in (1, kernel) -> floored to multiples of stride *
+    tensor_stride; otherwise every input + offset on that lattice and not below the inputs' per-axis minimum
+    (link_kmap_out_candidates).  Unique rows in (batch, x, y, z) order through link_index_cells on the lattice grid; ONE host
+    round trip (the number of sites).  Returns (coordinates int32[M,4], their TIGHT bounding box (lo, hi) where it follows
+    from the inputs' without a pass over the sites -- the floor rule: floor is monotone, so the floored extremes are attained
+    -- else None: on the candidate rule only a superset of the box is known (kernel < stride leaves lattice points between
+    the inputs' minimum and the first site), and a cached box's lower corner is what the NEXT candidate-rule layer filters
+    with, so none is handed out).  Raises GridTooLarge beyond the dense-grid limit and beyond 2^31 candidate rows: the
+    callers' torch / hash-chain path takes such frames."""
+    n, dev = coords.shape[0], coords.device
+    ss = [int(stride[k]) * int(tensor_stride[k]) for k in range(3)]
+    (lo, hi) = bounds
+    if n == 0:
+        return coords.new_empty((0, 4)), None
+    if all(int(stride[k]) in (1, int(kernel[k])) for k in range(3)):
+        glo = [lo[k] // ss[k] for k in range(3)]
+        ghi = [hi[k] // ss[k] for k in range(3)]
+        q = coords[:, :3] if ss == [1, 1, 1] else torch.div(coords[:, :3], _dev_i32(dev, ss), rounding_mode="floor")
+        rows = torch.cat([coords[:, 3:4], q], 1).int().contiguous()
+        tight = True
+    else:
+        glo = [-((-lo[k]) // ss[k]) for k in range(3)]                                       # first lattice point >= the minimum
+        ghi = [(hi[k] + (int(kernel[k]) // 2) * int(tensor_stride[k])) // ss[k] for k in range(3)]   # last one a tap can reach
+        if any(ghi[k] < glo[k] for k in range(3)):
+            return coords.new_empty((0, 4)), None
+        ncomb = int(L.lib().link_kmap_candidate_count(_i3(kernel), _i3(stride)))
+        if ncomb < 1:
+            raise L.LinkAmdError(f"kernel map builder: kernel {tuple(kernel)} / stride {tuple(stride)} not supported (extents 1..7)")
+        try:                                                    # the grid first: no candidate buffer for a frame that cannot use it
+            v = L.grid_from_bounds((lo[3], glo[0], glo[1], glo[2]), (hi[3], ghi[0], ghi[1], ghi[2]), 1).cells
+        except L.LinkAmdError as e:
+            raise GridTooLarge(str(e))
+        if v > MAX_CELLS:
+            raise GridTooLarge(f"dense grid would need {v} cells (> {MAX_CELLS})")
+        if n * ncomb >= 1 << 31:
+            raise GridTooLarge(f"{n} inputs x {ncomb} candidates: beyond the builder's 2^31 rows")
+        rows = torch.empty((n * ncomb, 4), dtype=torch.int32, device=dev)
+        tight = False
+        lo4 = (ctypes.c_int32 * 4)(int(lo[0]), int(lo[1]), int(lo[2]), int(lo[3]))
+        L.check(L.lib().link_kmap_out_candidates(coords.contiguous().data_ptr(), n, _i3(kernel), _i3(stride), _i3(tensor_stride),
+                                                 lo4, rows.data_ptr(), L.current_stream_handle()), "link_kmap_out_candidates")
+    sites, hdr = unique_cells(rows, ((lo[3], glo[0], glo[1], glo[2]), (hi[3], ghi[0], ghi[1], ghi[2])))
+    m = int(hdr[L.HDR_M].item())
+    scale = ss[0] if ss[0] == ss[1] == ss[2] else _dev_i32(dev, ss)
+    box = (tuple(glo[k] * ss[k] for k in range(3)) + (lo[3],), tuple(ghi[k] * ss[k] for k in range(3)) + (hi[3],))
+    return torch.cat([sites[:m, 1:4] * scale, sites[:m, 0:1]], 1).contiguous(), (box if tight and m > 0 else None)
