@@ -1049,6 +1049,47 @@ int link_streams_share_queue(void *stream_a, void *stream_b, double *delay_us /*
  * streams involved.  (link_dc_batch_create runs the same test to put its role streams on queues of their own.) */
 int link_dc_batch_probe_streams(link_dc_batch_t *ctx, hipStream_t stream, double *delays_us /* host [12] */);
 
+/* =============================================================================================
+ * I. Detection post-processing (csrc/boxnms.hip): rotated BEV overlap / IoU, NMS, CenterHead decode
+ *
+ * What the reference's CUDA-only extension iou3d_nms_cuda (detection/det3d/ops/iou3d_nms/src/iou3d_nms_kernel.cu) and the decode of
+ * CenterHead.predict (detection/det3d/models/bbox_heads/center_head.py:344-421,461-467) compute.  Boxes are float[n, 7] =
+ * x, y, z, dx, dy, dz, heading.  All fp32, no atomics, bitwise reproducible.  Additive entries: the ABI version does not move.
+ *
+ * NMS is two kernels: the suppression mask uint64[cap, ceil(cap / 64)] (bit c of word [i, cb] = box i suppresses box 64 cb + c;
+ * only the words with cb >= i / 64 are computed, and every one of those is written) and the reference's greedy scan
+ * (iou3d_nms.cpp:116-132) over it, on the device in one workgroup: keep int64[cap] = the kept indices in ascending order, then -1;
+ * count int32[1].  Boxes are taken in the order given (the caller sorts by score).  `n_dev`, when not NULL, is a device int32 with
+ * the number of boxes that count, clamped to [0, cap]: the row stride of the mask and the sizes of all buffers follow `cap`, so a
+ * caller with a fixed capacity never reads a size back.  post_max > 0 stops the scan after that many kept boxes.
+ * Predicates: LINK_NMS_ROTATE rotated IoU > thr; LINK_NMS_NORMAL IoU of the axis-aligned x, y, dx, dy rectangles > thr;
+ * LINK_NMS_CIRCLE squared distance of the centres <= thr (circle_nms_jit.py:23-27).
+ * n == 0 / cap == 0: LINK_OK, count 0 when a count pointer is given.  Null buffers with n > 0, thr not finite, an unknown predicate,
+ * more than 65535 * 16 boxes: LINK_ERR_ARG before anything touches a device.  link_nms_bev: LINK_ERR_WORKSPACE when the mask
+ * workspace is smaller than the bytes its size helper names.
+ * ============================================================================================= */
+#define LINK_NMS_ROTATE 0
+#define LINK_NMS_NORMAL 1
+#define LINK_NMS_CIRCLE 2
+int link_boxes_overlap_bev(const float *boxes_a, int64_t na, const float *boxes_b, int64_t nb, float *out /* [na, nb] */, void *stream);
+int link_boxes_iou_bev(const float *boxes_a, int64_t na, const float *boxes_b, int64_t nb, float *out /* [na, nb] */, void *stream);
+size_t link_nms_workspace_bytes(int64_t n);            /* 8 * n * ceil(n / 64); host only */
+int link_nms_mask(const float *boxes, int64_t cap, const int32_t *n_dev, int32_t pred, float thr, uint64_t *mask, void *stream);
+int link_nms_reduce(const uint64_t *mask, int64_t cap, const int32_t *n_dev, int32_t post_max, int64_t *keep /* [cap] */,
+                    int32_t *count /* [1] */, void *stream);
+int link_nms_bev(const float *boxes, int64_t cap, const int32_t *n_dev, int32_t pred, float thr, int32_t post_max, void *workspace,
+                 size_t workspace_bytes, int64_t *keep /* [cap] */, int32_t *count /* [1] */, void *stream);
+/* CenterHead decode of one task's NCHW maps, read in place: hm[B, K, H, W], reg[B, 2, H, W], height[B, 1, H, W], dim[B, 3, H, W],
+ * rot[B, 2, H, W] (sin, cos), vel[B, 2, H, W] or NULL.  Writes boxes float[B, H W, 7 or 9 with vel] = x, y, z, exp dims, (vel), heading;
+ * labels int32[B, H W] = the arg max class; scores float[B, H W] = the max sigmoid, -inf where the score is not above the threshold or
+ * the centre lies outside post_center_range (lo x, y, z, hi x, y, z); counts int32[B] = cells per frame that are not masked. */
+typedef struct {
+  float out_size_factor, voxel_size[2], pc_range[2], score_threshold, post_center_range[6];
+} link_center_geom_t;
+int link_center_decode(const float *hm, const float *reg, const float *height, const float *dim, const float *rot, const float *vel,
+                       int32_t batch, int32_t num_cls, int32_t h, int32_t w, const link_center_geom_t *geom /* host */, float *boxes,
+                       int32_t *labels, float *scores, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,15 @@ class LinkBlockArgs(Structure):
                 ("out", c_void_p), ("bbox", c_int32 * 8), ("stats", c_int32 * 4), ("verdict", c_int32), ("reserved", c_int32)]
 
 
+NMS_ROTATE, NMS_NORMAL, NMS_CIRCLE = 0, 1, 2
+
+
+class LinkCenterGeom(Structure):
+    """link_center_geom_t (section I: CenterHead decode)"""
+    _fields_ = [("out_size_factor", c_float), ("voxel_size", c_float * 2), ("pc_range", c_float * 2), ("score_threshold", c_float),
+                ("post_center_range", c_float * 6)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -279,6 +288,14 @@ SIGNATURES = {
     "link_streams_share_queue": (c_int, [c_void_p, c_void_p, POINTER(ctypes.c_double)]),
     "link_elk_mid_backward": (c_int, [c_void_p] * 9 + [POINTER(LinkGrid), c_void_p, c_void_p, c_void_p,
                                       POINTER(LinkElkDesc), c_int64, c_int64] + [c_void_p] * 5),
+    # section I: detection post-processing (csrc/boxnms.hip)
+    "link_boxes_overlap_bev": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "link_boxes_iou_bev": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "link_nms_workspace_bytes": (c_size_t, [c_int64]),
+    "link_nms_mask": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
+    "link_nms_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "link_nms_bev": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_float, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "link_center_decode": (c_int, [c_void_p] * 6 + [c_int32] * 4 + [POINTER(LinkCenterGeom)] + [c_void_p] * 5),
 }
 
 _lib = None
