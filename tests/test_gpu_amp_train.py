@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad64 as G
 from helpers import lidar_like, rel_err, s_uniform
 
 pytestmark = pytest.mark.gpu
@@ -36,22 +37,6 @@ def _run(fn, feats, coords, index, p, baseop, cg, r, div, gout):
     out = fn(f, coords, index, q["w_pre"], q["pre_ln_w"], q["pre_ln_b"], q["w_pos"], q["alpha"], q["ln_w"],
              q["ln_b"], baseop, cg, r, div, 1e-6)
     out.backward(gout)
-    grads = {"feats": f.grad}
-    grads.update({k: v.grad for k, v in q.items() if v is not None})
-    return out.detach(), grads
-
-
-def _oracle64(feats, coords, p, s, r, baseop, groups, div, gout):
-    from oracle import link_oracle as lo
-    f = feats.detach().cpu().double().requires_grad_(True)
-    q = {k: (v.detach().cpu().double().requires_grad_(True) if v is not None else None) for k, v in p.items()}
-    params = {"pre_mix.0.weight": q["w_pre"], "pre_mix.1.weight": q["pre_ln_w"], "pre_mix.1.bias": q["pre_ln_b"],
-              "pos_weight.0.weight": q["w_pos"], "norm.weight": q["ln_w"], "norm.bias": q["ln_b"]}
-    if q["alpha"] is not None:
-        params["alpha"] = q["alpha"]
-    out = lo.elk_core_torch(f, coords.cpu(), params, s, r, baseop, groups, variant="encoder" if div != 1.0 else "unet",
-                            tensor_stride=int(div), agg=lo.aggregate_torch)
-    out.backward(gout.cpu().double())
     grads = {"feats": f.grad}
     grads.update({k: v.grad for k, v in q.items() if v is not None})
     return out.detach(), grads
@@ -94,11 +79,18 @@ def test_core_train_half_rows_bit_equal_to_widened_fp32(dtype, C, groups, baseop
     for k in g32:
         if k != "feats":
             assert g16[k].dtype == torch.float32 and torch.equal(g16[k], g32[k]), k
-    o_r, g_r = _oracle64(f16.float(), coords, p, s, r, baseop, groups, div, gout)
+    # the float64 reference on the widened rows and its fp32 yardstick (tests/grad64.py; shared with test_gpu_train_gate.py)
+    key = (frame, 6000 if frame == "uniform" else 20000, C, groups, baseop, s, r, div, str(dtype))
+    g64, o32 = G.cached_yardstick(key, lambda: (f16, coords, p, s, r, baseop, groups, div, gout))
+    case = dict(suite="half_rows_bit_equal", C=C, groups=groups, op=baseop, s=s, r=r, n=n, div=div, rows=str(dtype)[6:])
+    rows = G.measure(case, g64, o32, dict(g16, out=o16), G.rounding_cost(g64, dtype))
     tol = TOL_ORACLE[dtype]
-    assert rel_err(o16.cpu().numpy(), o_r.numpy()) < tol
-    for k in g_r:
-        assert rel_err(g16[k].float().cpu().numpy(), g_r[k].numpy()) < tol, k
+    assert rel_err(o16.cpu().numpy(), g64["out"].numpy()) < tol
+    for k in g64:
+        if k != "out":
+            assert rel_err(g16[k].float().cpu().numpy(), g64[k].numpy()) < tol, k
+    bad = [row for row in rows if not row["ok"]]
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("dtype", HALF)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad64 as G
 from helpers import lidar_like, rel_err, s_uniform
 
 pytestmark = pytest.mark.gpu
@@ -34,22 +35,11 @@ def _run(fn, feats, coords, index, p, baseop, cg, r, div, gout):
     return out.detach(), grads
 
 
-def _oracle64(feats, coords, p, s, r, baseop, groups, div, gout):
-    """fp64 autograd over the oracle's torch restatement (CPU)."""
-    from oracle import link_oracle as lo
-    f = feats.detach().cpu().double().requires_grad_(True)
-    q = {k: (v.detach().cpu().double().requires_grad_(True) if v is not None else None) for k, v in p.items()}
-    params = {"pre_mix.0.weight": q["w_pre"], "pre_mix.1.weight": q["pre_ln_w"], "pre_mix.1.bias": q["pre_ln_b"],
-              "pos_weight.0.weight": q["w_pos"], "norm.weight": q["ln_w"], "norm.bias": q["ln_b"]}
-    if q["alpha"] is not None:
-        params["alpha"] = q["alpha"]
-    variant = "encoder" if div != 1.0 else "unet"
-    out = lo.elk_core_torch(f, coords.cpu(), params, s, r, baseop, groups, variant=variant,
-                            tensor_stride=int(div), agg=lo.aggregate_torch)
-    out.backward(gout.cpu().double())
-    grads = {"feats": f.grad}
-    grads.update({k: v.grad for k, v in q.items() if v is not None})
-    return out.detach(), grads
+def _reference(key, feats, coords, p, s, r, baseop, groups, div, gout):
+    """(out, gradients, g64, o32): fp64 autograd over the oracle's torch restatement and the fp32 yardstick of tests/grad64.py
+    (CPU; computed once per case and session)."""
+    g64, o32 = G.cached_yardstick(key, lambda: (feats, coords, p, s, r, baseop, groups, div, gout))
+    return g64["out"], {k: v for k, v in g64.items() if k != "out"}, g64, o32
 
 
 CASES = [
@@ -90,13 +80,21 @@ def test_train_path_vs_fp64_oracle_and_composition(C, groups, baseop, s, r, n, d
         assert n / index.M > 4                     # the cooperative mode is what this case is for
     o_t, g_t = _run(elk_core_train, feats, coords, index, p, baseop, cg, r, div, gout)
     o_a, g_a = _run(elk_core_autograd, feats, coords, index, p, baseop, cg, r, div, gout)
-    o_r, g_r = _oracle64(feats, coords, p, s, r, baseop, groups, div, gout)
+    key = ("train", frame, n, C, groups, baseop, s, r, div, "torch.float32")
+    o_r, g_r, g64, o32 = _reference(key, feats, coords, p, s, r, baseop, groups, div, gout)
+    # the per-tensor gate against what fp32 evaluation of the reference costs; its rows are written before any verdict
+    case = dict(suite="train_vs_composition", C=C, groups=groups, op=baseop, s=s, r=r, n=n, div=div, rows="float32")
+    rows = G.measure(case, g64, o32, dict(g_t, out=o_t))
     assert rel_err(o_t.cpu().numpy(), o_r.numpy()) < 1e-4
     for k in g_r:
         e_t = rel_err(g_t[k].cpu().numpy(), g_r[k].numpy())
         e_a = rel_err(g_a[k].cpu().numpy(), g_r[k].numpy())
+        print(f"{k}: e_t {e_t:.3e} e_a {e_a:.3e} o32 {o32[k]:.3e}  max(2e-4, 3 e_a) = {max(2e-4, 3 * e_a):.3e}  "
+              f"4 o32 + 2e-6 = {4 * o32[k] + 2e-6:.3e}")
         # fp32 sums over N voxels: allow what the op-by-op fp32 path itself needs, and 2e-4 absolute cap
         assert e_t < max(2e-4, 3 * e_a), (k, e_t, e_a)
+    bad = [row for row in rows if not row["ok"]]
+    assert not bad, bad
 
 
 def test_train_path_is_deterministic_and_used_by_module():
