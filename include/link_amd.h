@@ -38,7 +38,7 @@ extern "C" {
 /* Version of this ABI (bumped on any signature change). */
 int link_abi_version(void);
 /* sizeof of the structs crossing this boundary (0 link_grid_t, 1 link_elk_desc_t, 2 link_elk_buffers_t, 3 link_dc_grid_t,
- * 4 link_dc_tuning_t, 5 link_dc_buffers_t, 6 link_lean_buffers_t, 7 link_block_args_t; -1 otherwise): what a binding checks its own layout against. */
+ * 4 link_dc_tuning_t, 5 link_dc_buffers_t, 6 link_lean_buffers_t, 7 link_block_args_t, 8 link_voxelize_geom_t; -1 otherwise): what a binding checks its own layout against. */
 int32_t link_abi_struct_size(int32_t which);
 /* Human-readable last HIP error string of the calling thread ("" if none). Host pointer. */
 const char *link_last_error(void);
@@ -1089,6 +1089,55 @@ typedef struct {
 int link_center_decode(const float *hm, const float *reg, const float *height, const float *dim, const float *rot, const float *vel,
                        int32_t batch, int32_t num_cls, int32_t h, int32_t w, const link_center_geom_t *geom /* host */, float *boxes,
                        int32_t *labels, float *scores, int32_t *counts, void *stream);
+
+/* =============================================================================================
+ * J. Point clouds to voxels (csrc/voxelize.hip): the hard voxeliser with its mean reader, the dynamic voxeliser
+ *
+ * What the reference does on the host per frame, detection/det3d/ops/point_cloud/point_cloud_ops.py:8-55,112-184 (the numba loop
+ * points_to_voxel, called through core/input/voxel_generator.py:5-30 by datasets/pipelines/preprocess.py:171-217) followed by
+ * models/readers/voxel_encoder.py:17-24 (VoxelFeatureExtractorV3: mean of the kept rows), and what models/readers/
+ * dynamic_voxel_encoder.py:8-17,70-102 (virtual=False) does with torch.unique(dim=0) and a scatter mean.  Additive entries: the ABI
+ * version does not move.  Integer atomics only; every float sum runs in ascending point index, so two calls are bit for bit equal.
+ *
+ * points float[n, ndim] (x, y, z first) holds the clouds of `batch` samples one after the other; point_offsets int32[batch + 1]
+ * (device) names their rows, point_offsets[batch] (clamped to n_points_capacity, which sizes the launches and the workspace) is the
+ * number of points.  Every sample is voxelised on its own and the voxels are concatenated in sample order: voxel_offsets
+ * int32[batch + 1] (device, written) names the rows of each sample, clamped to voxel_capacity (voxels beyond it are not written).
+ * Outputs, rows past voxel_offsets[batch] zeroed: mean float[voxel_capacity, ndim]; coors int32[voxel_capacity, 4] = b, z, y, x
+ * (16-byte aligned); num_points int32[voxel_capacity]; voxels float[voxel_capacity, max_points, ndim] or NULL (hard mode only; a
+ * caller that wants the mean alone never materialises it).  No host synchronisation inside.
+ *
+ * LINK_VOXELIZE_HARD: c = floor((p - lo) / vs) per axis in float32 (an IEEE subtract and a correctly rounded divide), the point is
+ *   dropped unless 0 <= c < grid; voxels are numbered by the first point that falls into them, keep their first max_points points in
+ *   input order, and only the first max_voxels voxels of a sample exist (points of later cells are dropped); num_points =
+ *   min(count, max_points); mean = the sum of the kept rows / num_points.  `hi` is not read.
+ * LINK_VOXELIZE_DYNAMIC: the point is kept when lo <= p <= hi per axis (inclusive above, so a coordinate may equal grid),
+ *   c = trunc((p - lo) / vs); voxels in ascending (z, y, x) order; mean over ALL points of the voxel; max_points / max_voxels are
+ *   not read and `voxels` must be NULL.
+ * A coordinate that is not finite is out of range in both modes (the reference's behaviour on it is undefined).
+ * grid = round((hi - lo) / vs) in float32, half to even, computed by the caller.
+ *
+ * The workspace holds one bit per cell and sample plus forty bytes per point of capacity.  It must be ZERO before the first call
+ * and whenever geometry or batch change; every call leaves it as the next call needs it (n_points_capacity may differ from call to
+ * call while the workspace is large enough).
+ * One workspace serves one stream at a time.
+ * Errors, before anything is launched: LINK_ERR_ARG for ndim outside 3..16, a voxel size or grid that is not positive, an unknown
+ * mode, max_points / max_voxels < 1 in hard mode, batch outside 1..1024, a null pointer, and a grid that is too large (more than
+ * 2^28 cells per sample, 2^31 over all samples, or an axis of 2^24); LINK_ERR_WORKSPACE for a workspace smaller than the bytes the
+ * size helper names (which returns 0 where the call itself would return LINK_ERR_ARG).
+ * ============================================================================================= */
+#define LINK_VOXELIZE_HARD 0
+#define LINK_VOXELIZE_DYNAMIC 1
+typedef struct {
+  float lo[3], hi[3], vs[3];          /* x, y, z */
+  int32_t grid[3];                    /* x, y, z */
+  int32_t max_points, max_voxels, ndim, mode;
+} link_voxelize_geom_t;               /* link_abi_struct_size(8) */
+size_t link_voxelize_workspace_bytes(const link_voxelize_geom_t *geom /* host */, int64_t n_points_capacity, int32_t batch); /* host only */
+int link_voxelize(const link_voxelize_geom_t *geom /* host */, const float *points, const int32_t *point_offsets /* [batch + 1], device */,
+                  int32_t batch, int64_t n_points_capacity, void *workspace, size_t workspace_bytes, float *voxels /* nullable */,
+                  float *mean, int32_t *coors /* [voxel_capacity, 4] = b, z, y, x */, int32_t *num_points, int64_t voxel_capacity,
+                  int32_t *voxel_offsets /* [batch + 1], device */, void *stream);
 
 #ifdef __cplusplus
 }

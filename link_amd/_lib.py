@@ -112,6 +112,16 @@ class LinkCenterGeom(Structure):
                 ("post_center_range", c_float * 6)]
 
 
+VOXELIZE_HARD, VOXELIZE_DYNAMIC = 0, 1
+STRUCT_VOXELIZE_GEOM = 8                                      # its id for link_abi_struct_size (its place in the tuple lib() checks)
+
+
+class LinkVoxelizeGeom(Structure):
+    """link_voxelize_geom_t (section J: point clouds to voxels)"""
+    _fields_ = [("lo", c_float * 3), ("hi", c_float * 3), ("vs", c_float * 3), ("grid", c_int32 * 3), ("max_points", c_int32),
+                ("max_voxels", c_int32), ("ndim", c_int32), ("mode", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -296,6 +306,10 @@ SIGNATURES = {
     "link_nms_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "link_nms_bev": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_float, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "link_center_decode": (c_int, [c_void_p] * 6 + [c_int32] * 4 + [POINTER(LinkCenterGeom)] + [c_void_p] * 5),
+    # section J: point clouds to voxels (csrc/voxelize.hip)
+    "link_voxelize_workspace_bytes": (c_size_t, [POINTER(LinkVoxelizeGeom), c_int64, c_int32]),
+    "link_voxelize": (c_int, [POINTER(LinkVoxelizeGeom), c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_size_t] + [c_void_p] * 4 +
+                      [c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -320,7 +334,8 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
         if handle.link_abi_version() != ABI_VERSION:
             raise LinkAmdError("liblink_amd.so ABI version mismatch; rebuild with link_amd/build.py")
-        for which, cls in enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs)):
+        for which, cls in enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
+                                      LinkVoxelizeGeom)):
             if handle.link_abi_struct_size(which) != ctypes.sizeof(cls):
                 raise LinkAmdError(f"liblink_amd.so: layout of {cls.__name__} differs from include/link_amd.h "
                                    f"({ctypes.sizeof(cls)} bytes here, {handle.link_abi_struct_size(which)} in the library)")

@@ -88,9 +88,10 @@ def s_kitti(seed: int = 0, n_az: int = 4608, voxel: float = 0.05, return_points:
     return (coords, feats, pts) if return_points else (coords, feats)
 
 
-def s_nusc(seed: int = 0, n_az: int = 2180, sweeps: int = 10, max_points: int = 10):
+def s_nusc(seed: int = 0, n_az: int = 2180, sweeps: int = 10, max_points: int = 10, return_points: bool = False):
     """SURVEY 8d S-nusc.  Returns (coords int32 [N,4] in (x, y, z, batch) order on the 1440 x 1440 x 40 grid,
-    feats float32 [N,5] = per-voxel mean of at most `max_points` points over (x, y, z, intensity, dt))."""
+    feats float32 [N,5] = per-voxel mean of at most `max_points` points over (x, y, z, intensity, dt)); with return_points also the
+    frame's points float64 [P,5] before the crop, in sweep order (what link_amd.Voxelizer takes)."""
     rng = np.random.default_rng(seed)
     lo, hi = _scene(rng)
     allp = []
@@ -100,6 +101,7 @@ def s_nusc(seed: int = 0, n_az: int = 2180, sweeps: int = 10, max_points: int = 
         f = np.concatenate([p, rng.uniform(0, 1, (p.shape[0], 1)), np.full((p.shape[0], 1), 0.05 * k)], 1)
         allp.append(f)
     f = np.concatenate(allp)
+    points = f
     pmin = np.array([-54.0, -54.0, -5.0])
     pmax = np.array([54.0, 54.0, 3.0])
     ok = np.all((f[:, :3] >= pmin) & (f[:, :3] < pmax), 1)
@@ -119,7 +121,7 @@ def s_nusc(seed: int = 0, n_az: int = 2180, sweeps: int = 10, max_points: int = 
     feats = (sums / np.minimum(counts, max_points)[:, None]).astype(np.float32)
     coords = np.zeros((uniq.shape[0], 4), np.int32)
     coords[:, :3] = vox[start]
-    return coords, feats
+    return (coords, feats, points) if return_points else (coords, feats)
 
 
 def block_stats(coords: np.ndarray, s: int):
