@@ -785,7 +785,13 @@ typedef struct {
                           single-role form (cos_x, r = 2).  bit 3: pair consumers (the round-2 kernel) instead of quad consumers;
                           bit 0: single-role form (workgroup-wide dealing); bit 1: one voxel per lane group instead of a pair (pair
                           forms); bit 2: own-cell form (a lane group de-modulates its own cell from the A row in registers; 2-slot
-                          plane ring fed by a dedicated DMA wave; 39 KB of LDS) */
+                          plane ring fed by a dedicated DMA wave; 39 KB of LDS);
+                          bit 4 (quad consumers, r = 3): square rim tiles.  By default an axis of the block grid that is 4 m + 1 cells
+                          long has its last cell covered by 1 x 10 / 10 x 1 strips of columns instead of 4 x 4 tiles with one real
+                          column in four (37 x 37 blocks: 89 tiles instead of 100); the rows are the same bit for bit, the bit is
+                          what the strips are tested and measured against.  Measured on cfg2: the batch entry point gains 1.3 us / frame
+                          from the strips, three plans on three streams lose 2.8 -- the Python layer sets the bit
+                          on ElkCorePlan and clears it on ElkCoreBatch's arenas */
   int32_t mode;        /* 0 = default (7); else bit 0 fused pre_mix+modsum, bit 1 dense-cell demod kernel, bit 2 fused
                           gather + de-modulate (C = 64; the other widths keep box sum and de-modulation as two kernels: a fused form for them
                           measured slower and was removed in round 4) -- the unfused stages are what the fused ones are tested against */

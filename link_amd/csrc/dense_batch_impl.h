@@ -238,9 +238,10 @@ __global__ void __launch_bounds__(256 + 64 * (DC_K2Q_CW + (DC_K2Q_PMAP ? 1 : 0))
   static_assert(DC_K2Q_PMAP == 1, "the mapper wave draws the items");
   typedef const __attribute__((address_space(4))) dc_bt_k2_args_t *args_ptr_t;
   constexpr unsigned CTL_THREAD = 256 + 64 * DC_K2Q_CW;  // lane 0 of the mapper wave
-  __shared__ int s_ctl[2];                             // [0] frame of the item (-1: done), [1] bid for dc_k2q_body
+  // [0] frame of the item (-1: done), [1] bid for dc_k2q_body; the control thread's own state across a tile: [2] the item after the
+  // current one, [3] the workgroup's XCD (in LDS, not in registers: with three tile shapes in the body they were what spilled)
+  __shared__ int s_ctl[4];
   const int x = (int)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7u);
-  int t_next = 0;                                      // (control thread only) the item after the current one
   if (threadIdx.x == CTL_THREAD) {
     args_ptr_t a = (args_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     int32_t *sy = a->sync;
@@ -248,7 +249,8 @@ __global__ void __launch_bounds__(256 + 64 * (DC_K2Q_CW + (DC_K2Q_PMAP ? 1 : 0))
     if (DC_BT_PROF)                                    // when this workgroup became resident (row behind the items' rows; kind 7)
       bt_row(a->p.dbg2, (unsigned long long)a->nframes * (8 * per) + blockIdx.x, 9999, 0, __builtin_amdgcn_s_memrealtime(), 0, 0, blockIdx.x);
     const int t = __hip_atomic_fetch_add(&sy[bt_cursor(x)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t_next = __hip_atomic_fetch_add(&sy[bt_cursor(x)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_ctl[2] = __hip_atomic_fetch_add(&sy[bt_cursor(x)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_ctl[3] = x;
     int f = t < a->nframes * per ? t / per : -1;
     if (f >= 0 && !bt_wait_ge(sy, bt_k1(f), a->k1_target)) f = -1;
     s_ctl[0] = f; s_ctl[1] = f >= 0 ? (t - f * per) * 8 + x : 0;
@@ -272,13 +274,13 @@ __global__ void __launch_bounds__(256 + 64 * (DC_K2Q_CW + (DC_K2Q_PMAP ? 1 : 0))
       const unsigned long long tq1 = DC_BT_PROF ? __builtin_amdgcn_s_memrealtime() : 0;
       int32_t *sy = a->sync;
       const int per = (a->nwg + 7) >> 3;
-      const int t = t_next;
+      const int t = s_ctl[2], xc = s_ctl[3];
       int fn = t < a->nframes * per ? t / per : -1;
       if (fn >= 0) {
-        t_next = __hip_atomic_fetch_add(&sy[bt_cursor(x)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_ctl[2] = __hip_atomic_fetch_add(&sy[bt_cursor(xc)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (!bt_wait_ge(sy, bt_k1(fn), a->k1_target)) fn = -1;
       }
-      s_ctl[0] = fn; s_ctl[1] = fn >= 0 ? (t - fn * per) * 8 + x : 0;
+      s_ctl[0] = fn; s_ctl[1] = fn >= 0 ? (t - fn * per) * 8 + xc : 0;
       if (DC_BT_PROF) bt_row(a->p.dbg2, (unsigned long long)f * (8 * per) + bid, (unsigned long long)f, (unsigned long long)bid, tq0, tq1, __builtin_amdgcn_s_memrealtime(), (unsigned long long)blockIdx.x);
     }
     __syncthreads();                                   // the tile's LDS images are free again, the next item is laid out
@@ -289,10 +291,9 @@ __global__ void __launch_bounds__(256 + 64 * (DC_K2Q_CW + (DC_K2Q_PMAP ? 1 : 0))
 
 template <int OP, int R>
 static int batch_launch(const dc_bt_host_t &c, const dc_bt_frames_t &fr, const dc_bt_par_t &p, const link_dc_grid_t &g, const link_elk_desc_t &d,
-                        int nframes, int64_t nmax) {
+                        int nframes, int64_t nmax, bool strips) {
   using K1 = dc_k1_cfg<64, OP>;
   using KQ = dc_k2q_cfg<OP, R>;
-  using KG = typename dc_k2_cfg<OP, R>::G;
   // LDS is handed out in 128 granules of 1 280 bytes per CU (tools/coresidency_probe.hip: 81 152 + 81 920 bytes share a CU, 81 152 +
   // 82 048 do not; 82 944 + 80 304 do, 82 944 + 80 896 do not).  With their static LDS (K1: 256 B behind __syncthreads_or; K2: 16 B of
   // loop control) K1 is padded to 65 granules and K2 takes 63: one of each fills a CU, two K1 workgroups do not fit (the mix bench.py's
@@ -312,14 +313,15 @@ static int batch_launch(const dc_bt_host_t &c, const dc_bt_frames_t &fr, const d
   int cpw = (int)((vi + (int64_t)k1_wgs * K1::NW * rpw - 1) / ((int64_t)k1_wgs * K1::NW * rpw));
   if (cpw < 1) cpw = 1;
   const int k1_target = (int)((vi + cpw - 1) / cpw);    // ranges of a frame
-  const int txn = (g.dim[0] + KG::TX - 1) / KG::TX, tyn = (g.dim[1] + KG::TY - 1) / KG::TY;
+  // the tile list of the stand-alone quad kernel (launch_k2): square tiles, then the rim strips of axes of 4 m + 1 cells
+  const dc_k2q_tiles_t tq = dc_k2q_tiles(g, R, strips);
   // z-segments of a K2 tile: 1 = whole columns.  The stream geometry cuts columns in two so that ONE frame's tiles fill the chip; here
   // the K2 role's workgroups draw tiles of several frames, and whole columns are 5 % fewer plane steps (B = 32 x 2 sets, one box: 33.9
   // us / frame against 34.7 with two segments, 35.4 with three).  LINK_DC_BATCH_ZSPLIT (experiments only) overrides.
   static const int zs_env = [] { const char *e = getenv("LINK_DC_BATCH_ZSPLIT"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
   int zsplit = zs_env;
   if (zsplit > g.dim[2]) zsplit = g.dim[2];
-  const int64_t nwg = (int64_t)txn * tyn * g.dim[3] * zsplit;
+  const int64_t nwg = ((int64_t)tq.txn * tq.tyn + tq.nxs + tq.nys) * g.dim[3] * zsplit;
   if (nwg > (1 << 20)) return LINK_ERR_ARG;
   // insert items per frame: one per 256 voxels of the largest frame, NOT capped -- an item covers exactly its own 256 voxels, so a
   // cap dropped every voxel of a larger frame past cap x 256 (the cap of 2048 lost the voxels past 524 288 without a status bit).
@@ -339,7 +341,7 @@ static int batch_launch(const dc_bt_host_t &c, const dc_bt_frames_t &fr, const d
   hipLaunchKernelGGL((k_dc_batch_k1<OP, 2>), dim3((unsigned)k1_wgs), dim3(64 * K1::NW), k1_lds, c.sa, fr, p, g, nframes, cpw, k1_target, wpf, sync);
   rc = check_launch("link_elk_core_dense_forward_batch (K1)");
   if (rc != LINK_OK) return rc;
-  const dc_bt_k2_args_t a2{fr, p, g, nframes, txn, tyn, zsplit, (int)nwg, k1_target, sync};
+  const dc_bt_k2_args_t a2{fr, p, g, nframes, tq.txn, tq.tyn, zsplit, (int)nwg, k1_target, sync};
   static_assert(sizeof(dc_bt_k2_args_t) <= 4096, "kernel arguments");
   hipLaunchKernelGGL((k_dc_batch_k2<OP, R>), dim3((unsigned)c.cus), dim3(KQ::THREADS), k2_lds, c.sb, a2);
   return check_launch("link_elk_core_dense_forward_batch (K2)");
@@ -358,7 +360,10 @@ int batch_set_launch(const dc_bt_host_t &c, const link_dc_buffers_t *frames, con
                             b.hdr, b.out, n[i]};
     nmax = n[i] > nmax ? n[i] : nmax;
   }
-  if (d.op == LINK_OP_COS) return d.r == 3 ? batch_launch<LINK_OP_COS, 3>(c, fr, p, g, d, nb, nmax) : batch_launch<LINK_OP_COS, 2>(c, fr, p, g, d, nb, nmax);
-  return d.r == 3 ? batch_launch<LINK_OP_SIN, 3>(c, fr, p, g, d, nb, nmax) : batch_launch<LINK_OP_SIN, 2>(c, fr, p, g, d, nb, nmax);
+  // as in launch_k2: k2_form bit 4 = square rim tiles.  LINK_DC_BATCH_SQUARE_RIM=1 (experiments only) sets it for every call.
+  static const bool sq_env = [] { const char *e = getenv("LINK_DC_BATCH_SQUARE_RIM"); return e && atoi(e) != 0; }();
+  const bool strips = !(b0.tune.k2_form & 16) && !sq_env;
+  if (d.op == LINK_OP_COS) return d.r == 3 ? batch_launch<LINK_OP_COS, 3>(c, fr, p, g, d, nb, nmax, strips) : batch_launch<LINK_OP_COS, 2>(c, fr, p, g, d, nb, nmax, strips);
+  return d.r == 3 ? batch_launch<LINK_OP_SIN, 3>(c, fr, p, g, d, nb, nmax, strips) : batch_launch<LINK_OP_SIN, 2>(c, fr, p, g, d, nb, nmax, strips);
 }
 }  // namespace DC_IO_NS

@@ -925,13 +925,24 @@ static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const 
   if constexpr (dc_k2q_cfg<OP, R>::FITS) {             // two-part rows, theta shared by channels j / j + 32: quad consumers (bit 3: round-2 pair form)
     if (pair && !b->alpha && !(b->tune.k2_form & 9) && !k2_single) {
       using KQ = dc_k2q_cfg<OP, R>;
+      // the quad form's own tile list: 1 x 10 / 10 x 1 strips on the rim of an axis of 4 m + 1 cells (k2_form bit 4: square rim tiles,
+      // the launch of before -- what the strips are tested against bit for bit)
+      const dc_k2q_tiles_t tq = dc_k2q_tiles(g, R, !(b->tune.k2_form & 16));
+      const int64_t tiles = ((int64_t)tq.txn * tq.tyn + tq.nxs + tq.nys) * g.dim[3];
+      int zq = b->tune.k2_zsplit;
+      if (zq <= 0) {
+        zq = (int)(512 / tiles);
+        if (zq < 1) zq = 1;
+      }
+      if (zq > g.dim[2]) zq = g.dim[2];
+      const int64_t nwg_q = tiles * zq, grid_q = (nwg_q + 7) / 8 * 8;
 #define LINK_K2Q(DD)                                                                                                  \
   do {                                                                                                                \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather_demod_quad<OP, R, DD>),                     \
                               hipFuncAttributeMaxDynamicSharedMemorySize, KQ::LDS_BYTES + k2_pad);                   \
-    hipLaunchKernelGGL((k_dc_gather_demod_quad<OP, R, DD>), dim3((unsigned)grid), dim3(KQ::THREADS), KQ::LDS_BYTES + k2_pad, st, b->S, \
+    hipLaunchKernelGGL((k_dc_gather_demod_quad<OP, R, DD>), dim3((unsigned)grid_q), dim3(KQ::THREADS), KQ::LDS_BYTES + k2_pad, st, b->S, \
                        b->cell_n, reinterpret_cast<const int4 *>(b->slots), b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg, \
-                       d.coord_div, d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out,                                   \
+                       d.coord_div, d.eps, n, g, tq.txn, tq.tyn, zq, (int)nwg_q, b->out,                               \
                        reinterpret_cast<unsigned long long *>(b->tune.k2_dbg));                                       \
   } while (0)
       if (div) LINK_K2Q(true); else LINK_K2Q(false);

@@ -5,12 +5,16 @@
 
 namespace link {
 
-template <int C, int P, int R>
+// Tile shape (TX_, TY_) in output columns; 0 = the square default of the width.  The quad K2 (dense_gather_quad_impl.h) also runs
+// 1 x 10 and 10 x 1 strips on the grid's rim: their 3 x 12 halo is the 36 columns of the 4 x 4 tile's 6 x 6, so every size below
+// -- pieces, passes, LDS bytes -- stays what it is and only the column <-> (x, y) maps change.
+template <int C, int P, int R, int TX_ = 0, int TY_ = 0>
 struct dc_gather_cfg {
   static constexpr int LPR = C / 4;                  // C in {16,32,64,128}: power of two
   static constexpr int NG = 256 / LPR;               // groups per workgroup
-  static constexpr int TY = NG >= 64 ? 8 : (NG >= 16 ? 4 : 2);
-  static constexpr int TX = NG / TY;
+  static constexpr int TY = TY_ > 0 ? TY_ : (NG >= 64 ? 8 : (NG >= 16 ? 4 : 2));
+  static constexpr int TX = TX_ > 0 ? TX_ : NG / TY;
+  static_assert(TX * TY <= NG, "an output column per lane group");
   static constexpr int HLO = (R == 3) ? 1 : 0;
   static constexpr int HX = TX + R - 1, HY = TY + R - 1;
   static constexpr int NCOL = HX * HY;
@@ -107,9 +111,9 @@ __device__ __forceinline__ void dc_read_dx(uint32_t ra, uint32_t ca, float4 (&cu
 // ONE LDS latency plus the transfers instead of three dependent round trips.  Guide section 5.7 form (ii): every statement
 // that waits names the registers that become valid there as "+v", so nothing consumes them earlier; the sums are formed in
 // the order dc_read_dx forms them (bitwise identical results).  Needs 27 more registers than the one-offset-at-a-time form.
-template <int C>
+template <int C, int TX_ = 0, int TY_ = 0>
 __device__ __forceinline__ void dc_read_plane_p2r3(uint32_t ra, uint32_t ca, float4 (&cur)[2], float &cc) {
-  using K = dc_gather_cfg<C, 2, 3>;
+  using K = dc_gather_cfg<C, 2, 3, TX_, TY_>;
   constexpr int RB = 2 * C * 4;
 #define O_(dx, dy, pp) "i"((((dx) * K::HY + (dy)) * RB) + (pp) * C * 4)
 #define Q_(dx, dy) "i"(((dx) * K::HY + (dy)) * 4)

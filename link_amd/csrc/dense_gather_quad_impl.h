@@ -50,9 +50,9 @@
                             ops -- the difference is one rounding, 6e-8 relative, next to the hardware trig's 4e-7) */
 #endif
 
-template <int OP, int R>
+template <int OP, int R, int TX_ = 0, int TY_ = 0>
 struct dc_k2q_cfg {
-  using K2 = dc_k2_cfg<OP, R>;
+  using K2 = dc_k2_cfg<OP, R, TX_, TY_>;
   static constexpr int PAR_OFF = K2::SPLIT_LDS_BYTES;            // LayerNorm weight | bias image (2 x 64 floats)
   // count images run two planes ahead of the row images (the producers look a plane's counts up before they request its
   // rows): a ring of five 256-byte images (the tile's <= 64 haloed columns, requested by every producer wave alike) laid
@@ -142,19 +142,33 @@ __device__ __forceinline__ float dc_quad_sum(float v) {
   return v;
 }
 
-// the kernel body as a device function of the workgroup number `bid` (see dc_k1m_body)
+// Tile shapes of the quad form.  SH 0: the 4 x 4 tile.  SH 1 / 2 (r = 3): a 1 x 10 / 10 x 1 strip of output columns along the grid's
+// x / y rim, used where a grid axis is 4 m + 1 cells long -- the last cell then costs a strip per ten columns instead of a 4 x 4
+// tile per four, each marching every z-plane (cfg2's 37 x 37 blocks: 81 + 8 tiles instead of 100).  A strip's 3 x 12 halo is the 36
+// columns of the square tile's 6 x 6: the same plane ring, A images, record images and LDS bytes; lane groups, record columns and
+// map cells beyond the strip's ten stay idle.  A cell's sums are formed in the same order in every shape (3 x 3 in the plane, then
+// the z ring), so the rows do not depend on the tiling.
+template <int SH> struct dc_k2q_shape { static constexpr int TX = 0, TY = 0; };
+template <> struct dc_k2q_shape<1> { static constexpr int TX = 1, TY = 10; };
+template <> struct dc_k2q_shape<2> { static constexpr int TX = 10, TY = 1; };
+#define DC_K2Q_STRIP 10                                  /* output columns of a strip */
+
+// one tile: batch item b, output columns [x0, x0 + TX) x [y0, y0 + TY) cut at the grid, z-segment zseg of zsplit; L = its linear number
 // COH (round 6, the persistent batch kernel of dense_batch.hip): the tables were stored write-through by ANOTHER workgroup of a
 // launch that is still running -> every global read (plane DMA, counts, records) is an sc1 load (L2-served, never the CU's L1), which
 // replaces an agent-scope acquire per tile (MI355X_MICROARCH.md "inter-workgroup visibility").  false: plain loads behind a kernel
 // boundary, as ever.
-template <int OP, int R, bool DIV, bool COH = false>
-__device__ __forceinline__ void dc_k2q_body(
+template <int OP, int R, bool DIV, bool COH, int SH>
+__device__ __forceinline__ void dc_k2q_tile(
     const float *__restrict__ S_, const int32_t *__restrict__ cell_n, const int4 *__restrict__ slots,
     const float *__restrict__ w_pos, const float *__restrict__ alpha, const float *__restrict__ ln_w,
-    const float *__restrict__ ln_b, int cg, float coord_div, float eps, int64_t n, const link_dc_grid_t &g, int txn, int tyn,
-    int zsplit, int nwg, void *__restrict__ out, unsigned long long *__restrict__ dbg, const int bid, const unsigned tidx) {
-  using K2 = dc_k2_cfg<OP, R>;
-  using KQ = dc_k2q_cfg<OP, R>;
+    const float *__restrict__ ln_b, int cg, float coord_div, float eps, int64_t n, const link_dc_grid_t &g, const int b, const int x0,
+    const int y0, const int zseg, int zsplit, void *__restrict__ out,
+    unsigned long long *__restrict__ dbg, const int L, const unsigned tidx) {
+  using K2 = dc_k2_cfg<OP, R, dc_k2q_shape<SH>::TX, dc_k2q_shape<SH>::TY>;
+  using KQ = dc_k2q_cfg<OP, R, dc_k2q_shape<SH>::TX, dc_k2q_shape<SH>::TY>;
+  static_assert(K2::G::HX * K2::G::HY <= 36 && K2::G::TX * K2::G::TY <= K2::NG, "a tile shape within the 4 x 4 tile's halo and lane groups");
+  static_assert(KQ::LDS_BYTES == dc_k2q_cfg<OP, R>::LDS_BYTES && K2::NI == dc_k2_cfg<OP, R>::NI, "every shape runs in the square tile's LDS layout");
   DC_PROF_PTR(dbg);
   // optional per-wave timing (tools/k2prof.py): s_memtime ticks waiting for the plane DMA, in the barrier, in the box sums /
   // the quad round
@@ -162,34 +176,16 @@ __device__ __forceinline__ void dc_k2q_body(
   int tq_rounds = 0;
   using K = typename K2::G;
   constexpr int C = 64, P = 2, TY = K::TY, TX = K::TX, HY = K::HY, HLO = K::HLO;
+  constexpr int NT = TX * TY;                          // output columns of the tile (<= NG: lane groups, record columns, map cells beyond stay idle)
   constexpr int RB = P * C * 4;
   static_assert(K2::P == 2, "two-part rows");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const bool producer = tidx < 256;
   const int tid = tidx & 255, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane((tidx & 255) >> 6);
-  const int per = (nwg + 7) >> 3;
-  const int L = (bid & 7) * per + (bid >> 3);
-  if (L >= nwg) return;
-  int t = L;
-  const int zseg = t % zsplit; t /= zsplit;
-#if DC_K2_MAP
-  // tiles of one batch item enumerated y-half by y-half: a contiguous range of L (what one XCD runs) is then ~2.5 x 5 tiles
-  // instead of ~1.25 x 10 -- fewer halo rows fetched into two L2s
-  const int per_b = txn * tyn;
-  const int b = t / per_b;
-  int tt2 = t - b * per_b;
-  const int H = (tyn + 1) >> 1;
-  int tx, ty;
-  if (tt2 < txn * H) { tx = tt2 / H; ty = tt2 - tx * H; }
-  else { tt2 -= txn * H; const int H2 = tyn - H; tx = tt2 / H2; ty = H + tt2 - tx * H2; }
-#else
-  const int ty = t % tyn; t /= tyn;
-  const int tx = t % txn;
-  const int b = t / txn;
-#endif
-  const int Dx = g.dim[0], Dy = g.dim[1], Dz = g.dim[2];
+  // A y-rim strip stops in front of the corner cell where the x-rim has strips as well (they take the corner): both axes follow one
+  // rule, so the x-rim has them iff dim[0] = 4 m + 1.  (Read off the grid, not passed in: the batch kernel has no scalar register to spare.)
+  const int Dx = g.dim[0] - ((SH == 2 && (g.dim[0] & 3) == 1) ? 1 : 0), Dy = g.dim[1], Dz = g.dim[2];
   const int PDx = g.pdim[0], PDy = g.pdim[1], PDz = g.pdim[2];
-  const int x0 = tx * TX, y0 = ty * TY;
   const int zs = (int)(((long long)Dz * zseg) / zsplit), ze = (int)(((long long)Dz * (zseg + 1)) / zsplit);
   if (zs >= ze) return;
   const int nplanes = (ze - zs) + R - 1;
@@ -241,7 +237,8 @@ __device__ __forceinline__ void dc_k2q_body(
     int rec_k;
     {
       const int piece = wave * 16 + (lane & 15);
-      const int col = piece >> 2;
+      int col = piece >> 2;
+      if constexpr (NT < K2::NG) col = col < NT ? col : NT - 1;
       rec_k = piece & 3;
       rec_cell0 = col_cell0(col / TY + HLO, col % TY + HLO);
     }
@@ -273,10 +270,17 @@ __device__ __forceinline__ void dc_k2q_body(
     // share of the plane DMA and keeps the barriers.  Wave w owns columns ix = w (groups 4w .. 4w+3 = iy 0..3), which makes whole
     // waves idle on the x rim only; on the y rim the (group -> column) map is transposed (wave w owns iy = w).  The A image and
     // the counts stay addressed by the canonical cell number ix * TY + iy the mapper and the consumers use.
-    const bool rim_t = DC_K2Q_RIM && (y0 + TY > Dy) && (x0 + TX <= Dx);      // workgroup-uniform
-    const int ix = rim_t ? grp % TX : grp / TY, iy = rim_t ? grp / TX : grp % TY;
-    const int cell = ix * TY + iy;
-    const bool col_ok = (x0 + ix < Dx) && (y0 + iy < Dy);
+    // A strip (NT < NG) has no transposed form: its groups 0 .. NT - 1 are its columns in order, the groups behind them own no column
+    // (they read column 0 and write an A row no consumer is sent to, with a count of 0).
+    const bool rim_t = DC_K2Q_RIM && SH == 0 && (y0 + TY > Dy) && (x0 + TX <= Dx);      // workgroup-uniform
+    int ix = rim_t ? grp % TX : grp / TY, iy = rim_t ? grp / TX : grp % TY;
+    bool grp_ok = true;
+    if constexpr (NT < K2::NG) {
+      grp_ok = grp < NT;
+      ix = grp_ok ? ix : 0; iy = grp_ok ? iy : 0;
+    }
+    const int cell = grp_ok ? ix * TY + iy : grp;
+    const bool col_ok = grp_ok && (x0 + ix < Dx) && (y0 + iy < Dy);
     const bool wave_has = (DC_K2Q_RIM && DC_K2Q_PMAP) ? __any(col_ok) : true;   // wave-uniform
     if (!wave_has && li == 0) {                        // its cells hold nothing in any plane: both count images say so once (the
       lds_wr_b32(ncnt0 + (uint32_t)(cell * 4), 0);     // consumers walk them for planes of more than 64 voxels)
@@ -312,7 +316,7 @@ __device__ __forceinline__ void dc_k2q_body(
       {
         const uint32_t ra = bufa + row_lane, ca = lds_base + cnt_slot(i, m3) + cnt_lane;
         if constexpr (R == 3) {
-          dc_read_plane_p2r3<C>(ra, ca, cur, cc);
+          dc_read_plane_p2r3<C, dc_k2q_shape<SH>::TX, dc_k2q_shape<SH>::TY>(ra, ca, cur, cc);
         } else {
           dc_read_dx<C, P, R, 0>(ra, ca, cur, cc);
           dc_read_dx<C, P, R, 1>(ra, ca, cur, cc);
@@ -370,7 +374,8 @@ __device__ __forceinline__ void dc_k2q_body(
       if (i >= nplanes) break;
       const uint32_t ca = lds_base + (uint32_t)(m3 * K2::SPLIT_BUF_BYTES + K2::SPLIT_PLANE);
       int run = 0, c_ = 0, start = 0;
-#define Q_(k) "i"(((((k) / TY) + HLO) * HY + ((k) % TY) + HLO) * 4)
+#define QK_(k) ((k) < NT ? (k) : 0)                    /* map cells beyond the tile's columns: counted as empty, read in place */
+#define Q_(k) "i"((((QK_(k) / TY) + HLO) * HY + (QK_(k) % TY) + HLO) * 4)
 #define DC_MAP4(K0)                                                                                                          \
       {                                                                                                                      \
         int n0, n1, n2, n3;                                                                                                  \
@@ -382,7 +387,7 @@ __device__ __forceinline__ void dc_k2q_body(
         const int nn[4] = {n0, n1, n2, n3};                                                                                  \
         _Pragma("unroll") for (int kk = 0; kk < 4; kk++) {                                                                   \
           const int k = K0 + kk;                                                                                             \
-          const bool okk = (x0 + k / TY < Dx) && (y0 + k % TY < Dy);   /* wave-uniform: columns beyond the grid hold nothing */ \
+          const bool okk = k < NT && (x0 + k / TY < Dx) && (y0 + k % TY < Dy);   /* wave-uniform: columns beyond the grid hold nothing */ \
           run += okk ? nn[kk] : 0;                                                                                           \
           if (k < 15) {                                                                                                      \
             const bool le = run <= lane;                                                                                     \
@@ -394,6 +399,7 @@ __device__ __forceinline__ void dc_k2q_body(
       DC_MAP4(0) DC_MAP4(4) DC_MAP4(8) DC_MAP4(12)
 #undef DC_MAP4
 #undef Q_
+#undef QK_
       const uint32_t mb = lds_base + (uint32_t)(KQ::MAP_OFF + m3 * KQ::MAP_BYTES);
       lds_wr_b32(mb + (uint32_t)(lane * 4), (c_ << 12) | ((lane - start) & 4095));
       if (lane == 0) lds_wr_b32(mb + 256u, run);
@@ -579,6 +585,68 @@ __device__ __forceinline__ void dc_k2q_body(
   if (dbg && lane == 0) {
     unsigned long long *d = dbg + ((size_t)L * 8 + (tidx >> 6)) * 8;
     d[0] = DC_NOW() - tq0; d[1] = tq0; d[2] = tq_bar; d[3] = 0; d[4] = tq_work; d[5] = tq_rounds; d[6] = nplanes; d[7] = 2;
+  }
+}
+
+// Tiles of a launch, in the order of their linear number: the square tiles of every batch item (txn x tyn each), then the rim strips
+// of every batch item -- the x-rim's (x = dim[0] - 1, every y, the corner included), then the y-rim's (y = dim[1] - 1, the x below the
+// x-rim strip).  The launcher chooses strips per axis by sending the square tiles' counts: an axis whose square tiles stop one cell
+// short of the grid (txn * TX == dim[0] - 1) has a strip.  dc_k2q_tiles() is the host's side of the same enumeration.
+struct dc_k2q_tiles_t { int txn, tyn, nxs, nys; };
+static inline dc_k2q_tiles_t dc_k2q_tiles(const link_dc_grid_t &g, int r, bool strips) {
+  const bool sx = strips && r == 3 && (g.dim[0] & 3) == 1, sy = strips && r == 3 && (g.dim[1] & 3) == 1;
+  const int dxs = g.dim[0] - (sx ? 1 : 0), dys = g.dim[1] - (sy ? 1 : 0);
+  return dc_k2q_tiles_t{(dxs + 3) / 4, (dys + 3) / 4, sx ? (g.dim[1] + DC_K2Q_STRIP - 1) / DC_K2Q_STRIP : 0,
+                        sy ? (dxs + DC_K2Q_STRIP - 1) / DC_K2Q_STRIP : 0};
+}
+
+// the kernel body as a device function of the workgroup number `bid` (see dc_k1m_body): decodes (shape, x0, y0, zseg) and runs the tile
+template <int OP, int R, bool DIV, bool COH = false>
+__device__ __forceinline__ void dc_k2q_body(
+    const float *__restrict__ S_, const int32_t *__restrict__ cell_n, const int4 *__restrict__ slots,
+    const float *__restrict__ w_pos, const float *__restrict__ alpha, const float *__restrict__ ln_w,
+    const float *__restrict__ ln_b, int cg, float coord_div, float eps, int64_t n, const link_dc_grid_t &g, int txn, int tyn,
+    int zsplit, int nwg, void *__restrict__ out, unsigned long long *__restrict__ dbg, const int bid, const unsigned tidx) {
+  using KS = typename dc_k2_cfg<OP, R>::G;
+  const int per = (nwg + 7) >> 3;
+  const int L = (bid & 7) * per + (bid >> 3);
+  if (L >= nwg) return;
+  int t = L;
+  const int zseg = t % zsplit; t /= zsplit;
+  const bool sx = txn * KS::TX < g.dim[0], sy = tyn * KS::TY < g.dim[1];      // rim strips on this axis (r = 3 launches only)
+  const int per_b = txn * tyn;
+  const int nsq = per_b * g.dim[3];
+  if (R != 3 || t < nsq) {
+#if DC_K2_MAP
+    // tiles of one batch item enumerated y-half by y-half: a contiguous range of L (what one XCD runs) is then ~2.5 x 5 tiles
+    // instead of ~1.25 x 10 -- fewer halo rows fetched into two L2s
+    const int b = t / per_b;
+    int tt2 = t - b * per_b;
+    const int H = (tyn + 1) >> 1;
+    int tx, ty;
+    if (tt2 < txn * H) { tx = tt2 / H; ty = tt2 - tx * H; }
+    else { tt2 -= txn * H; const int H2 = tyn - H; tx = tt2 / H2; ty = H + tt2 - tx * H2; }
+#else
+    const int ty = t % tyn; t /= tyn;
+    const int tx = t % txn;
+    const int b = t / txn;
+#endif
+    dc_k2q_tile<OP, R, DIV, COH, 0>(S_, cell_n, slots, w_pos, alpha, ln_w, ln_b, cg, coord_div, eps, n, g, b, tx * KS::TX, ty * KS::TY, zseg, zsplit,
+                                    out, dbg, L, tidx);
+    return;
+  }
+  if constexpr (R == 3) {
+    const int dxs = g.dim[0] - (sx ? 1 : 0);
+    const int nxs = sx ? (g.dim[1] + DC_K2Q_STRIP - 1) / DC_K2Q_STRIP : 0, nys = sy ? (dxs + DC_K2Q_STRIP - 1) / DC_K2Q_STRIP : 0;
+    int u = t - nsq;
+    const int b = u / (nxs + nys);
+    u -= b * (nxs + nys);
+    if (u < nxs)                                       // workgroup-uniform: one shape per tile
+      dc_k2q_tile<OP, R, DIV, COH, 1>(S_, cell_n, slots, w_pos, alpha, ln_w, ln_b, cg, coord_div, eps, n, g, b, g.dim[0] - 1, u * DC_K2Q_STRIP,
+                                      zseg, zsplit, out, dbg, L, tidx);
+    else
+      dc_k2q_tile<OP, R, DIV, COH, 2>(S_, cell_n, slots, w_pos, alpha, ln_w, ln_b, cg, coord_div, eps, n, g, b, (u - nxs) * DC_K2Q_STRIP,
+                                      g.dim[1] - 1, zseg, zsplit, out, dbg, L, tidx);
   }
 }
 

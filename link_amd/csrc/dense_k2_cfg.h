@@ -3,11 +3,12 @@
 // dense_batch.hip (round 6: the persistent K2-role kernel runs dc_k2q_body of dense_gather_quad_impl.h over (frame, tile) items).
 #pragma once
 
-template <int OP, int R>
+// (TX_, TY_): the tile shape of dc_gather_cfg, 0 = the 4 x 4 default (the quad form's rim strips are the only other shapes)
+template <int OP, int R, int TX_ = 0, int TY_ = 0>
 struct dc_k2_cfg {
   static constexpr int C = 64, LPR = 16, NG = 16;
   static constexpr int P = (OP == LINK_OP_COSX) ? 3 : 2;
-  using G = dc_gather_cfg<C, P, R>;
+  using G = dc_gather_cfg<C, P, R, TX_, TY_>;
   static constexpr int RB = P * C * 4;
   static constexpr int REC_OFF = G::PLANE_BYTES + G::CNT_BYTES;
   static constexpr int REC_BYTES = NG * DC_INL * 16;
@@ -25,7 +26,7 @@ struct dc_k2_cfg {
   static constexpr int SPLIT_LDS_BYTES = SPLIT_REC_OFF + 4 * REC_BYTES;
   static constexpr bool SPLIT_FITS = 2 * SPLIT_LDS_BYTES <= 160 * 1024;      // two workgroups per CU (not cos_x: 3-part rows)
   static constexpr int NI = G::PASSES + 2;            // DMA instructions per plane and wave
-  static_assert(G::NG == NG && G::TX * G::TY == NG, "16 columns");
+  static_assert(G::NG == NG && G::TX * G::TY <= NG && (TX_ > 0 || G::TX * G::TY == NG), "16 columns");
 };
 
 __device__ __forceinline__ void lds_rd2_b128(uint32_t a0, uint32_t a1, v4f_t &x0, v4f_t &x1) {

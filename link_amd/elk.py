@@ -354,6 +354,10 @@ class ElkCorePlan:
         multi = self.frames_in_flight > 1
         t.k1_wgs, t.k2_zsplit = (256, 2) if multi else (512, 0)
         t.k1_lds_pad = t.k2_lds_pad = t.k1_form = t.k2_form = t.mode = 0
+        # square rim tiles (k2_form bit 4) for plans run frame by frame: with three frames in flight on streams the gather kernel's
+        # rim strips measured 36.5 against 33.8 us / frame (docs/experiments.md "Rim strips") and one frame alone was not measured;
+        # the batch entry point, where they pay (31.7 against 33.0), clears the bit on its arenas.  k2_form=0 turns the strips on.
+        t.k2_form = 16
         if not multi and not self.sparse and self.c in (32, 64) and self.baseop != "cos_x" and "k1_form" not in kw:
             # one frame alone: the matrix-core sums form at four waves per SIMD (4096 waves) -- 49.6-50.3 us per step against
             # 52.8-53.3 for the cell-range form (A/B on one box, round 4); with frames in flight the cell-range form at one
@@ -537,6 +541,8 @@ class ElkCoreBatch:
         if int(self.plans[0].dcg.k) > 352:
             raise L.LinkAmdError("ElkCoreBatch: slot capacity above 352")
         self.n_cap, self.c, self.device = n_cap, c, device
+        for p in self.plans:
+            p.buf.tune.k2_form = 0                               # rim strips in the gather role (ElkCorePlan.set_tuning has the figures)
         self._bufs = (L.LinkDcBuffers * frames)()
         self._n = (ctypes.c_int64 * frames)()
         if share is not None:
