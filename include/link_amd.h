@@ -1145,6 +1145,52 @@ int link_voxelize(const link_voxelize_geom_t *geom /* host */, const float *poin
                   float *mean, int32_t *coors /* [voxel_capacity, 4] = b, z, y, x */, int32_t *num_points, int64_t voxel_capacity,
                   int32_t *voxel_offsets /* [batch + 1], device */, void *stream);
 
+/* =============================================================================================
+ * K. Segmentation criterion (csrc/segloss.hip): cross-entropy + Lovasz-softmax, forward and gradient, in one call
+ *
+ * What the reference's trainer computes per step, segmentation/core/trainers.py:64-73 with the pair core/builder.py:61-72 builds:
+ * nn.CrossEntropyLoss(ignore_index=255)(outputs, targets) + lovasz_softmax(softmax(outputs), targets, ignore=0), the latter being
+ * core/lovasz_losses.py:156-225 (flatten_probas: a nonzero(); lovasz_softmax_flat: a Python loop over the classes with a host
+ * test `fg.sum() == 0`, a full sort, a gather, lovasz_grad:21-33 = two cumsums and a shifted difference, a dot).  Additive entries:
+ * the ABI version does not move.  No host synchronisation, no allocation, integer atomics only; every float sum has a fixed
+ * order, so two calls on the same inputs are bit for bit equal.  The launches are sized by (n, c) alone and read the counts they
+ * need from the workspace, so a call can be captured in a graph.
+ *
+ * rows [n, c] in io_dtype (LINK_IO_F32 / F16 / BF16), widened to fp32 on load; labels int64 [n]; LINK_SEGLOSS_MIN_CLASSES <= c <=
+ * LINK_SEGLOSS_MAX_CLASSES and n * c < 2^31 - 2048.
+ * input_kind LINK_SEGLOSS_LOGITS: p = softmax(rows) in fp32; CE = the mean over rows with label != ce_ignore (and inside [0, c):
+ *   a label outside the range never indexes anything) of -log p[label]  (F.cross_entropy(rows.float(), labels, ignore_index),
+ *   0 / 0 = NaN when no row counts, as torch returns it).
+ * input_kind LINK_SEGLOSS_PROBAS: p = rows (lovasz_losses.py:156-202 itself: probabilities in [0, 1]); CE = 0 and unit_grad is d/dp.
+ * Lovasz: rows with label != lov_ignore are valid (all rows when use_lov_ignore == 0); a valid row whose label lies outside
+ *   [0, c) is background for every class (lovasz_losses.py:188 does the same).  For every class taken -- n_c > 0 valid rows of that
+ *   label with LINK_SEGLOSS_PRESENT, every class with LINK_SEGLOSS_ALL -- the errors e = |[y = c] - p_c| are sorted descending,
+ *   stable in row order, and loss_c = sum_k e_(k) g_k with lovasz_grad:21-33 in closed form, F_k / B_k the inclusive foreground /
+ *   background counts and U_k = n_c + B_k:  g_k = 1 / U_k (foreground), (n_c - F_k) / (U_{k-1} U_k) (background; 1 where U_{k-1} = 0).
+ *   lovasz = the mean of loss_c over the classes taken, 0 when none is or no row is valid.  g_k is a constant of the gradient, as
+ *   in the reference (lovasz_losses.py:201 wraps it in Variable()); d/dp = -+g / n_taken, 0 where e == 0.
+ * out float[3] (device) = total, CE, lovasz.  A non-finite p makes lovasz (and the total) NaN.
+ * unit_grad float[c, n] (device, CLASS-MAJOR, the caller's; written in full): d total / d rows for an upstream gradient of 1
+ *   (d lovasz / d p with LINK_SEGLOSS_PROBAS).  link_segloss_backward writes grad_rows[n, c] = unit_grad * upstream[0] in io_dtype,
+ *   rounded once; upstream is a DEVICE scalar (a GradScaler's scale lives there).
+ * The workspace holds 20 bytes per (row, class) plus the sort's tile histograms; it needs no initialisation and serves one
+ * stream at a time.  Errors, before anything is launched: LINK_ERR_ARG for a null pointer, n < 0, c or n * c outside the range, an
+ * unknown io_dtype / input_kind / classes; LINK_ERR_WORKSPACE for fewer bytes than link_segloss_workspace_bytes names (host only,
+ * needs no device; 0 where the call would return LINK_ERR_ARG).
+ * ============================================================================================= */
+#define LINK_SEGLOSS_LOGITS 0
+#define LINK_SEGLOSS_PROBAS 1
+#define LINK_SEGLOSS_PRESENT 0
+#define LINK_SEGLOSS_ALL 1
+#define LINK_SEGLOSS_MIN_CLASSES 2
+#define LINK_SEGLOSS_MAX_CLASSES 32
+size_t link_segloss_workspace_bytes(int64_t n, int32_t c); /* host only */
+int link_segloss_forward(const void *rows, int32_t io_dtype, int32_t input_kind, const int64_t *labels, int64_t n, int32_t c,
+                         int64_t ce_ignore, int64_t lov_ignore, int32_t use_lov_ignore, int32_t classes, void *workspace,
+                         size_t workspace_bytes, float *out /* [3] */, float *unit_grad /* [c, n] */, void *stream);
+int link_segloss_backward(const float *unit_grad /* [c, n] */, const float *upstream /* device scalar */, int64_t n, int32_t c,
+                          int32_t io_dtype, void *grad_rows /* [n, c] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,11 @@ class LinkVoxelizeGeom(Structure):
                 ("max_voxels", c_int32), ("ndim", c_int32), ("mode", c_int32)]
 
 
+SEGLOSS_LOGITS, SEGLOSS_PROBAS = 0, 1                         # link_segloss_forward::input_kind
+SEGLOSS_PRESENT, SEGLOSS_ALL = 0, 1                           # link_segloss_forward::classes
+SEGLOSS_MIN_CLASSES, SEGLOSS_MAX_CLASSES = 2, 32
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -310,6 +315,11 @@ SIGNATURES = {
     "link_voxelize_workspace_bytes": (c_size_t, [POINTER(LinkVoxelizeGeom), c_int64, c_int32]),
     "link_voxelize": (c_int, [POINTER(LinkVoxelizeGeom), c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_size_t] + [c_void_p] * 4 +
                       [c_int64, c_void_p, c_void_p]),
+    # section K: segmentation criterion, cross-entropy + Lovasz-softmax (csrc/segloss.hip)
+    "link_segloss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "link_segloss_forward": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p,
+                                     c_size_t, c_void_p, c_void_p, c_void_p]),
+    "link_segloss_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

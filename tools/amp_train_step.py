@@ -3,6 +3,11 @@ cos_x, s = 3, r = 2) on an S-kitti frame (link_amd/synth.py), in fp32 and under 
 reference trainer's amp_enabled mode): forward, cross-entropy (UNet) / sum of squares (encoder), backward, SGD step.
 
     python tools/amp_train_step.py [--net unet|encoder|both] [--steps 5] [--warmup 2] [--n-az 4608] [--profile]
+                                   [--criterion cross_entropy|lovasz_softmax] [--lovasz-impl fused|torch_loop]
+
+--criterion lovasz_softmax is the loss the reference's configs train with (CrossEntropyLoss(ignore_index=255) + lovasz_softmax(...,
+ignore=0), trainers.py:64-73): by default link_amd.SegCriterion (csrc/segloss.hip), with --lovasz-impl torch_loop the torch
+restatement of the reference's loop in tools/segloss_bench.py.  The default stays plain cross-entropy.
 
 Prints one JSON line per (net, mode): ms per step (median of --steps after --warmup, HIP events), peak memory of the
 timed steps.  --profile re-runs every (net, mode) in a child process under `rocprofv3 --kernel-trace --stats` and adds
@@ -19,9 +24,10 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> dict:
+def _run(net_name: str, amp: bool, steps: int, warmup: int, n_az: int, criterion: str = "cross_entropy", impl: str = "fused") -> dict:
     import torch
     import link_amd as la
     from harness import networks as N
@@ -36,6 +42,12 @@ def _run(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> dict:
     else:
         net = N.build_reference_shaped_encoder(la, 64, "cos_x", 1)
     net = net.to(dev).train()
+    if criterion == "cross_entropy":
+        crit = torch.nn.functional.cross_entropy
+    elif impl == "fused":
+        crit = la.SegCriterion()
+    else:
+        from segloss_bench import torch_loop_criterion as crit
     opt = torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9)
     scaler = torch.amp.GradScaler("cuda", enabled=amp)
 
@@ -44,7 +56,7 @@ def _run(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> dict:
         with torch.autocast("cuda", torch.float16, enabled=amp):
             x = la.SparseTensor(feats, coords, 1)
             if net_name == "unet":
-                loss = torch.nn.functional.cross_entropy(net(x), labels)
+                loss = crit(net(x), labels)
             else:
                 _, outs = net(x, 3, 2)
                 loss = outs[-1].F.float().square().mean()
@@ -67,6 +79,7 @@ def _run(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> dict:
         times.append(a.elapsed_time(b))
     times.sort()
     return {"net": net_name, "mode": "fp16_autocast" if amp else "fp32", "voxels": int(coords.shape[0]),
+            "criterion": criterion if criterion == "cross_entropy" or net_name != "unet" else f"{criterion}:{impl}",
             "ms_per_step": round(times[len(times) // 2], 2), "ms_min": round(times[0], 2),
             "peak_mem_mib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1), "loss": float(loss)}
 
@@ -88,7 +101,7 @@ def _profile(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> di
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tmp, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--net", net_name, "--mode", "amp" if amp else "fp32",
-               "--steps", str(steps), "--warmup", str(warmup), "--n-az", str(n_az)]
+               "--steps", str(steps), "--warmup", str(warmup), "--n-az", str(n_az)] + EXTRA
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=600)
         files = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
         if not files:
@@ -107,7 +120,11 @@ def _profile(net_name: str, amp: bool, steps: int, warmup: int, n_az: int) -> di
             **{f"at_native_{k}_per_step": round(v / per, 1) for k, v in counts.items()}}
 
 
+EXTRA = []                                                     # --criterion / --lovasz-impl, handed on to the profiled child
+
+
 def main():
+    global EXTRA
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", default="both", choices=["unet", "encoder", "both"])
     ap.add_argument("--mode", default="both", choices=["fp32", "amp", "both"])
@@ -115,12 +132,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n-az", type=int, default=4608)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--criterion", default="cross_entropy", choices=["cross_entropy", "lovasz_softmax"])
+    ap.add_argument("--lovasz-impl", default="fused", choices=["fused", "torch_loop"])
     a = ap.parse_args()
+    EXTRA = ["--criterion", a.criterion, "--lovasz-impl", a.lovasz_impl]
     nets = ["unet", "encoder"] if a.net == "both" else [a.net]
     modes = [False, True] if a.mode == "both" else [a.mode == "amp"]
     for net in nets:
         for amp in modes:
-            res = _run(net, amp, a.steps, a.warmup, a.n_az)
+            res = _run(net, amp, a.steps, a.warmup, a.n_az, a.criterion, a.lovasz_impl)
             if a.profile:
                 res.update(_profile(net, amp, 3, 1, a.n_az))
             print(json.dumps(res), flush=True)
