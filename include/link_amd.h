@@ -1191,6 +1191,104 @@ int link_segloss_forward(const void *rows, int32_t io_dtype, int32_t input_kind,
 int link_segloss_backward(const float *unit_grad /* [c, n] */, const float *upstream /* device scalar */, int64_t n, int32_t c,
                           int32_t io_dtype, void *grad_rows /* [n, c] */, void *stream);
 
+/* =============================================================================================
+ * L. CenterHead training (csrc/centerloss.hip): target assignment, focal loss and L1 regression loss, forward and gradient
+ *
+ * What the reference does on the host per sample, detection/det3d/datasets/pipelines/preprocess.py:283-467 (AssignLabel: a numpy loop
+ * over objects with gaussian_radius and draw_umich_gaussian of det3d/core/utils/center_utils.py:17-63), and what
+ * det3d/models/losses/centernet_loss.py (FastFocalLoss, RegLoss: a permuted copy of every map, a gather, `if num_pos == 0` on the
+ * host) and det3d/models/bbox_heads/center_head.py:248-293 (CenterHead.loss: in-place sigmoid and clamp, a torch.cat of five maps,
+ * .cpu() on two results per task) compute per step.  Additive entries: the ABI version does not move.  fp32 arithmetic unless
+ * stated, integer atomics only, every float sum in a fixed order (two calls are bit for bit equal), no host synchronisation, no
+ * allocation, launch geometry a function of the shapes alone: every call can be captured in a graph.
+ *
+ * link_center_assign: the targets of all tasks of a batch in one call (two launches).
+ *   gt_boxes float[batch, n_cap, 9] = x, y, z, w, l, h, vx, vy, rot (the nuScenes order AssignLabel reads); gt_classes
+ *   int32[batch, n_cap] = the global 1-based class, 0 (or anything outside 1..sum of num_classes) for an empty slot.  Task t owns the
+ *   global classes after those of the tasks before it, num_classes[t] of them.  Per task t, written in full, zeros included:
+ *   hm float[batch, num_classes[t], h, w]; anno_box float[batch, max_objs, 10]; ind int64[batch, max_objs]; mask uint8[batch, max_objs];
+ *   cat int64[batch, max_objs].
+ *   Slot order: a task's objects class by class, in input order inside a class (the task_masks / np.concatenate of lines 320-348);
+ *   only the first max_objs count; object k of that order owns slot k whether or not it is drawn (new_idx = k).
+ *   Sizes and centre: w' = w / vs[0] / osf, l' = l / vs[1] / osf, ct = ((x - lo) / vs) / osf, every operation an IEEE fp32 one rounded on
+ *   its own.  Cell ct_int = truncation toward zero: a centre in (-1, 0) lands in cell 0 with a negative offset.  An object with
+ *   w' <= 0, l' <= 0 or a cell outside the map is skipped: its slot stays zero.  (NaN sizes or centres are skipped as well.)
+ *   Radius = max(min_radius, int(gaussian_radius((l', w'), gaussian_overlap))), the three quadratic roots in float64.
+ *   Heat map: exp(-(dx^2 + dy^2) / (2 sigma^2)), sigma = (2 r + 1) / 6, in float64, rounded once to fp32, over the window
+ *   [x - min(x, r), x + min(w - x, r + 1)) x [y - min(y, r), y + min(h - y, r + 1)) (the left / right / top / bottom clipping of
+ *   draw_umich_gaussian), combined by max: the values are >= 0, so an integer atomic max on the bit pattern is order-independent.
+ *   The reference's cut `h[h < eps * h.max()] = 0` never fires: the smallest value of a window is exp(-36 r^2 / (2 r + 1)^2) > e^-9.
+ *   anno_box row = ct - ct_int (2), z, log w, log l, log h, vx, vy, sin rot', cos rot' with rot' = rot - floor(rot / P + 0.5) * P,
+ *   P = fp32(2 pi), in fp32 with separate roundings (limit_period); log / sin / cos in float64, rounded once.
+ *   ind = y * w + x; cat = the class inside the task, 0-based.
+ *   Errors, before anything touches a device: LINK_ERR_ARG for a null pointer, batch < 1, n_cap outside 0..LINK_CENTER_MAX_OBJECTS,
+ *   num_tasks outside 1..LINK_CENTER_MAX_TASKS, a class count outside 1..LINK_CENTER_MAX_CLASSES, w / h / max_objs / out_size_factor
+ *   < 1, min_radius < 0, batch * classes * h * w or batch * max_objs * 10 >= 2^31, a voxel size that is not positive, an overlap
+ *   outside (0, 1).  n_cap == 0: every target is written as zeros.
+ *
+ * link_center_loss_forward / link_center_loss_backward: one task's loss, three launches / two launches.
+ *   hm [batch, k, h, w] and the regression maps reg [batch, 2, h, w], height [.., 1, ..], dim [.., 3, ..], vel [.., 2, ..] or NULL,
+ *   rot [.., 2, ..] are read in place as NCHW in io_dtype (LINK_IO_F32 / F16 / BF16), widened on load; the targets are those of
+ *   link_center_assign (mask holds 0 or 1).  reg_batch_strides, when not NULL, names for reg, height, dim, vel, rot the elements from
+ *   one frame of the map to the next (at least channels * h * w), so that the five maps may be channel slices of ONE [batch, 10 or 8,
+ *   h, w] tensor (RegLoss's `output`); NULL: every map contiguous.  Either term may be left out: hm == NULL (with hm_target, cat,
+ *   unit_hm / grad_hm) gives hm_loss = 0 and a slot then counts whatever its cat; reg == height == dim == rot == NULL (with vel,
+ *   anno_box, code_weights, unit_box and the five gradients) gives loc_loss = 0.  code_weights float[10] (host): with vel all ten, without vel the first eight weigh the
+ *   target columns 0, 1, 2, 3, 4, 5, 8, 9.
+ *   input_kind LINK_CENTER_LOGITS: y = clamp(sigmoid(x), 1e-4, 1 - 1e-4) (CenterHead._sigmoid), its derivative included and zero
+ *   where the clamp is active (inclusive at the bounds, torch's rule).  LINK_CENTER_PROBAS: y = the map (FastFocalLoss itself).
+ *   neg = sum over the map of log(1 - y) y^2 (1 - t)^4; pos = sum over slots of mask log(y[b, cat, ind]) (1 - y)^2; num_pos = sum mask;
+ *   hm_loss = -(pos + neg) / num_pos, -neg when num_pos == 0 (selected on the device); box_loss[c] = sum over slots of
+ *   mask |pred[b, c, ind] - target[b, m, c]| / (num_pos + 1e-4); loc_loss = sum_c box_loss[c] code_weights[c];
+ *   loss = hm_loss + weight * loc_loss.
+ *   out float[16] (device) = loss, hm_loss, loc_loss, num_pos, box_loss[0..9] (zero past the last column), two spare entries (zero).
+ *   A logit that is not finite makes the loss and its gradient NaN (the reference clamps sigmoid(inf) to a finite loss with a zero
+ *   gradient; a GradScaler has to see the overflow).
+ *   Two deliberate differences from the reference: a slot with mask == 0 is not read at all (the reference multiplies by 0, so a NaN
+ *   there poisons its sums), and an ind or cat outside the map never indexes anything (such a slot counts in num_pos and in nothing
+ *   else).
+ *   Forward also writes the gradients for an upstream of 1: unit_hm float[batch, k, h, w] (dense) and unit_box
+ *   float[batch, max_objs, 10] (per slot and column, zero for a slot that does not count); both the caller's, written in full.
+ *   link_center_loss_backward multiplies by upstream[0], a DEVICE scalar (a GradScaler's scale lives there), and writes every
+ *   gradient tensor in full in io_dtype, rounded once: d hm dense, the regression gradients zero except at the ind cells.  Slots of
+ *   one frame that share a cell ADD in ascending slot order, by the thread that owns the lowest slot.
+ *   Sums: a workgroup's part by a tree of fixed shape, the workgroups' parts in workgroup order by one workgroup.
+ *   The workspace (link_center_loss_workspace_bytes; host only) holds the partial sums; it needs no initialisation and serves one
+ *   stream at a time.  Errors, before anything touches a device: LINK_ERR_ARG for a null pointer (vel / grad_vel excepted, which go
+ *   together), batch / k / h / w < 1, k > LINK_CENTER_MAX_CLASSES, batch * k * h * w or batch * 3 * h * w >= 2^31, max_objs outside
+ *   1..LINK_CENTER_MAX_SLOTS, batch > LINK_CENTER_MAX_BATCH, an unknown io_dtype / input_kind; LINK_ERR_WORKSPACE for fewer bytes than
+ *   the size helper names (0 where the call would return LINK_ERR_ARG).
+ * ============================================================================================= */
+#define LINK_CENTER_LOGITS 0
+#define LINK_CENTER_PROBAS 1
+#define LINK_CENTER_MAX_TASKS 8
+#define LINK_CENTER_MAX_CLASSES 16
+#define LINK_CENTER_MAX_OBJECTS 2048
+#define LINK_CENTER_MAX_SLOTS 4096
+#define LINK_CENTER_MAX_BATCH 1024
+typedef struct {
+  float pc_range[2], voxel_size[2];   /* x, y */
+  float gaussian_overlap;
+  int32_t out_size_factor, w, h, max_objs, min_radius, num_tasks;
+  int32_t num_classes[LINK_CENTER_MAX_TASKS];
+} link_center_assign_geom_t;          /* link_abi_struct_size(9) */
+int link_center_assign(const link_center_assign_geom_t *geom /* host */, const float *gt_boxes /* [batch, n_cap, 9] */,
+                       const int32_t *gt_classes /* [batch, n_cap] */, int32_t batch, int32_t n_cap,
+                       float *const *hm /* host [num_tasks] of device pointers, as the four below */, float *const *anno_box,
+                       int64_t *const *ind, uint8_t *const *mask, int64_t *const *cat, void *stream);
+size_t link_center_loss_workspace_bytes(int32_t batch, int32_t k, int32_t h, int32_t w, int32_t max_objs); /* host only */
+int link_center_loss_forward(const void *hm, const void *reg, const void *height, const void *dim, const void *vel /* nullable */,
+                             const void *rot, const int64_t *reg_batch_strides /* host [5], nullable */, int32_t io_dtype, int32_t input_kind, const float *hm_target, const float *anno_box,
+                             const int64_t *ind, const uint8_t *mask, const int64_t *cat, int32_t batch, int32_t k, int32_t h, int32_t w,
+                             int32_t max_objs, const float *code_weights /* host [10] */, float weight, void *workspace,
+                             size_t workspace_bytes, float *out /* [16] */, float *unit_hm /* [batch, k, h, w] */,
+                             float *unit_box /* [batch, max_objs, 10] */, void *stream);
+int link_center_loss_backward(const float *unit_hm, const float *unit_box, const int64_t *ind, const uint8_t *mask,
+                              const float *upstream /* device scalar */, int32_t batch, int32_t k, int32_t h, int32_t w, int32_t max_objs,
+                              int32_t io_dtype, void *grad_hm, void *grad_reg, void *grad_height, void *grad_dim,
+                              void *grad_vel /* nullable */, void *grad_rot, const int64_t *reg_batch_strides /* host [5], nullable */,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

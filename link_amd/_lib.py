@@ -127,6 +127,18 @@ SEGLOSS_PRESENT, SEGLOSS_ALL = 0, 1                           # link_segloss_for
 SEGLOSS_MIN_CLASSES, SEGLOSS_MAX_CLASSES = 2, 32
 
 
+CENTER_LOGITS, CENTER_PROBAS = 0, 1                           # link_center_loss_forward::input_kind
+CENTER_MAX_TASKS, CENTER_MAX_CLASSES, CENTER_MAX_OBJECTS, CENTER_MAX_SLOTS, CENTER_MAX_BATCH = 8, 16, 2048, 4096, 1024
+STRUCT_CENTER_ASSIGN_GEOM = 9                                 # its id for link_abi_struct_size
+
+
+class LinkCenterAssignGeom(Structure):
+    """link_center_assign_geom_t (section L: CenterHead target assignment)"""
+    _fields_ = [("pc_range", c_float * 2), ("voxel_size", c_float * 2), ("gaussian_overlap", c_float), ("out_size_factor", c_int32),
+                ("w", c_int32), ("h", c_int32), ("max_objs", c_int32), ("min_radius", c_int32), ("num_tasks", c_int32),
+                ("num_classes", c_int32 * 8)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -320,6 +332,12 @@ SIGNATURES = {
     "link_segloss_forward": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p,
                                      c_size_t, c_void_p, c_void_p, c_void_p]),
     "link_segloss_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    # section L: CenterHead training -- target assignment, focal + L1 loss (csrc/centerloss.hip)
+    "link_center_assign": (c_int, [POINTER(LinkCenterAssignGeom), c_void_p, c_void_p, c_int32, c_int32] + [POINTER(c_void_p)] * 5 + [c_void_p]),
+    "link_center_loss_workspace_bytes": (c_size_t, [c_int32] * 5),
+    "link_center_loss_forward": (c_int, [c_void_p] * 6 + [POINTER(c_int64), c_int32, c_int32] + [c_void_p] * 5 + [c_int32] * 5 + [POINTER(c_float), c_float, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "link_center_loss_backward": (c_int, [c_void_p] * 5 + [c_int32] * 6 + [c_void_p] * 6 + [POINTER(c_int64), c_void_p]),
 }
 
 _lib = None
@@ -345,7 +363,7 @@ def lib() -> ctypes.CDLL:
         if handle.link_abi_version() != ABI_VERSION:
             raise LinkAmdError("liblink_amd.so ABI version mismatch; rebuild with link_amd/build.py")
         for which, cls in enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
-                                      LinkVoxelizeGeom)):
+                                      LinkVoxelizeGeom, LinkCenterAssignGeom)):
             if handle.link_abi_struct_size(which) != ctypes.sizeof(cls):
                 raise LinkAmdError(f"liblink_amd.so: layout of {cls.__name__} differs from include/link_amd.h "
                                    f"({ctypes.sizeof(cls)} bytes here, {handle.link_abi_struct_size(which)} in the library)")

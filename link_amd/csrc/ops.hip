@@ -30,6 +30,7 @@ extern "C" int32_t link_abi_struct_size(int32_t which) {
     case 6: return (int32_t)sizeof(link_lean_buffers_t);
     case 7: return (int32_t)sizeof(link_block_args_t);
     case 8: return (int32_t)sizeof(link_voxelize_geom_t);
+    case 9: return (int32_t)sizeof(link_center_assign_geom_t);
     default: return -1;
   }
 }
