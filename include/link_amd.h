@@ -1289,6 +1289,85 @@ int link_center_loss_backward(const float *unit_hm, const float *unit_box, const
                               void *grad_vel /* nullable */, void *grad_rot, const int64_t *reg_batch_strides /* host [5], nullable */,
                               void *stream);
 
+/* =============================================================================================
+ * M. Segmentation front end and validation (csrc/segio.hip): quantise point clouds to voxels by a sort, vote, count for mIoU
+ *
+ * What the reference does on the host per frame: torchsparse.utils.quantize.sparse_quantize (segmentation/torchsparse-u/torchsparse/
+ * utils/quantize.py:9-46: a numpy ravel hash and np.unique with return_index and return_inverse) behind the rounding and the minimum
+ * subtraction of segmentation/core/datasets/semantic_kitti.py:219-220; and per validation step segmentation/evaluate.py:120-134 (voxel
+ * logits back to points through inverse_map, the test-time-augmentation passes stacked, summed, argmax) followed by core/callbacks.py:
+ * 41-52 (MeanIoU: 3 (num_classes - 1) read-backs).  Additive entries: the ABI version does not move.  Integer atomics only, no host
+ * synchronisation, no allocation, launch geometry a function of the shapes alone (every call can be captured in a graph); every
+ * result is an integer, so two calls are bit for bit equal.
+ *
+ * link_seg_quantize: `batch` clouds one after the other, point_offsets int32[batch + 1] (device; point_offsets[0] = 0, ascending)
+ *   names their rows, point_offsets[batch] (clamped to n, which sizes the launches and the workspace) is the number of points.
+ *   mode LINK_SEGQ_INT: points = int32[n, 3], the coordinates themselves (ndim and voxel_size are not read).
+ *   mode LINK_SEGQ_ROUND: points = float[n, ndim] (x, y, z first); the coordinate is rint(p / voxel_size), a correctly rounded fp32
+ *     divide, rounded half to even, then converted to int32: np.round(block[:, :3] / voxel_size).astype(np.int32).
+ *   In both modes the minimum of every axis over the sample is subtracted (pc_ -= pc_.min(0); the x -= min of ravel_hash).
+ *   Per sample the voxels are the distinct coordinates in ascending lexicographic (x, y, z) order, x most significant (the order
+ *   the ravel hash induces); the samples' voxels are concatenated in sample order.  Outputs:
+ *     coords int32[voxel_capacity, 4] = x, y, z, b after the minimum is subtracted (16-byte aligned); rows past the total zeroed;
+ *     indices int32[voxel_capacity]: the smallest point index of the voxel (what np.unique's return_index gives), indexing the
+ *       concatenated points; entries past the total zeroed;
+ *     inverse int32[n]: the voxel of every point as a row of coords (global); inverse_local int32[n] (nullable): the same counted from
+ *       the first voxel of the point's sample (what evaluate.py indexes one scene with).  -1 for a point of a flagged sample, for a
+ *       point whose voxel lies at or past voxel_capacity, and for the entries past the number of points: nothing ever names a row
+ *       that does not exist;
+ *     voxel_offsets int32[batch + 1]: the rows of each sample, clamped to voxel_capacity (voxels beyond it are not written);
+ *     status int32[4] = the voxel total before clamping, the flag word, the number of key bits sorted, the number of points.
+ *   Flags: LINK_SEGQ_FLAG_EXTENT -- an axis of a sample spans 2^20 or more after the minimum is subtracted, or a rounded coordinate
+ *   leaves int32; LINK_SEGQ_FLAG_NONFINITE -- a coordinate is NaN or infinite.  A sample that raises either produces zero voxels; the
+ *   other samples are not affected.  The sort key holds x, y, z in the bits the largest extent of each axis over the batch needs and
+ *   the sample index on top; LINK_SEGQ_FLAG_KEYBITS -- together they exceed 64 bits (possible only with more than 16 samples of
+ *   extents near 2^20): then no sample produces a voxel.
+ *   The sort is a stable LSD radix sort of (64-bit key, point index) pairs in tiles of LINK_SEGQ_SORT_TILE pairs, 8 bits per pass;
+ *   the passes above the highest key bit return at once, decided on the device.  33 launches whatever the data.
+ *   The workspace (link_seg_quantize_workspace_bytes; host only, needs no device) holds 24.5 bytes per point -- two key buffers, two
+ *   index buffers, the tile histograms -- plus 32 bytes per sample; it needs no initialisation and serves one stream at a time.
+ *   Errors, before anything is launched: LINK_ERR_ARG for n outside [0, 2^28), batch outside 1..1024, voxel_capacity outside
+ *   [0, 2^28), an unknown mode, with LINK_SEGQ_ROUND ndim outside 3..16 or a voxel size that is not positive and finite, a null
+ *   pointer (points and inverse may be null when n == 0, coords and indices when voxel_capacity == 0, inverse_local always);
+ *   LINK_ERR_WORKSPACE for fewer bytes than the size helper names (which returns 0 where the call would return LINK_ERR_ARG).
+ *
+ * link_seg_vote_eval: one kernel, one thread per point.
+ *   input_kind LINK_SEGEVAL_ROWS: rows [n_rows, c] in io_dtype (LINK_IO_F32 / F16 / BF16), LINK_SEGLOSS_MIN_CLASSES <= c <=
+ *     LINK_SEGLOSS_MAX_CLASSES; inverse int32[votes, n_points] names rows: pass v of point p reads rows[inverse[v, p]], an entry
+ *     outside [0, n_rows) contributes nothing (inverse == NULL: votes == 1, n_rows == n_points, point p reads row p).  The votes
+ *     (1..LINK_SEGEVAL_MAX_VOTES) are summed in fp32 in ascending pass order, starting from zero; the class is the arg max, the
+ *     lowest class index among equals; a NaN sum counts as -inf and never wins (class 0 when every sum is NaN or -inf).
+ *   input_kind LINK_SEGEVAL_PREDICTIONS: rows = int64[n_points], the classes themselves (the training-time callback receives
+ *     arg-maxed outputs); io_dtype, n_rows, inverse and votes are not read.
+ *   pred int32[n_points] (nullable) = the class, or lut[class] when lut int32[c] is given (the remap of evaluate.py:215-243; the
+ *   counters always take the class itself).  labels int64[n_points] (nullable: then nothing is counted); a point counts when
+ *   label != ignore_label.  counters int64[3, c] = seen, positive, correct; the call ADDS to them (the caller zeroes them once per
+ *   epoch):  seen[t] += 1 when 0 <= t < c;  positive[class] += 1 when 0 <= class < c;  correct[t] += 1 when class == t.
+ *   Per workgroup a histogram in LDS, then at most 3 c 64-bit integer atomics.
+ *   Errors, before anything is launched: LINK_ERR_ARG for c outside the range, n_points outside [0, 2^31), an unknown input_kind or
+ *   io_dtype, votes outside the range, n_rows outside [0, 2^31), labels without counters, null rows with points to read.
+ *   n_points == 0: LINK_OK, nothing is launched.
+ * ============================================================================================= */
+#define LINK_SEGQ_INT 0
+#define LINK_SEGQ_ROUND 1
+#define LINK_SEGQ_SORT_TILE 2048
+#define LINK_SEGQ_FLAG_EXTENT 1
+#define LINK_SEGQ_FLAG_NONFINITE 2
+#define LINK_SEGQ_FLAG_KEYBITS 4
+#define LINK_SEGEVAL_ROWS 0
+#define LINK_SEGEVAL_PREDICTIONS 1
+#define LINK_SEGEVAL_MAX_VOTES 16
+size_t link_seg_quantize_workspace_bytes(int64_t n, int32_t batch); /* host only */
+int link_seg_quantize(const void *points, int32_t mode, int32_t ndim, float voxel_size, const int32_t *point_offsets /* [batch + 1], device */,
+                      int32_t batch, int64_t n, void *workspace, size_t workspace_bytes, int32_t *coords /* [voxel_capacity, 4] = x, y, z, b */,
+                      int32_t *indices /* [voxel_capacity] */, int64_t voxel_capacity, int32_t *inverse /* [n] */,
+                      int32_t *inverse_local /* [n], nullable */, int32_t *voxel_offsets /* [batch + 1], device */, int32_t *status /* [4] */,
+                      void *stream);
+int link_seg_vote_eval(const void *rows, int32_t io_dtype, int32_t input_kind, int64_t n_rows, int32_t c,
+                       const int32_t *inverse /* [votes, n_points], nullable */, int32_t votes, int64_t n_points,
+                       const int64_t *labels /* nullable */, int64_t ignore_label, const int32_t *lut /* [c], nullable */,
+                       int32_t *pred /* [n_points], nullable */, int64_t *counters /* [3, c] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .aggregate import (aux_to_voxel, large_to_small, link_index_of, small_to_la
                         voxel_to_aux)
 from .elk import (Conv3d, ELKBlock, ElkCoreBatch, ElkCorePlan, SparseConvTensor, TSELKBlock, elk_core_autograd, elk_core_fused,
                   invalidate_derived_weights, spconv2ts, ts2spconv)
-from . import boxnms, centerloss, dethead, segloss, voxelize
+from . import boxnms, centerloss, dethead, segio, segloss, voxelize
 from .boxnms import (boxes_iou3d_gpu, boxes_iou_bev, boxes_overlap_bev, circle_nms, install_as_iou3d_nms, nms_gpu, nms_normal_gpu,
                      nms_padded, rotate_nms_pcdet, to_pcdet)
 from .centerloss import CenterHeadLoss, CenterTargetAssigner, FastFocalLoss, RegLoss
@@ -20,6 +20,7 @@ from .detstage import ELKv3Stage, SparseBasicBlock, SparseConv3d, SpMiddleResNet
 from .functional import calc_ti_weights, spcount, spdevoxelize, sphash, sphashquery, spvoxelize
 from .index import BlockIndex, coords_bounds
 from .modules import BatchNorm, LeakyReLU, ReLU, fapply, fuse_for_inference
+from .segio import SegEvaluator, SegVoxelizer, sparse_collate, sparse_collate_fn, sparse_quantize
 from .segloss import SegCriterion, lovasz_softmax, lovasz_softmax_flat
 from .pointvoxel import initial_voxelize, point_to_voxel, voxel_to_point
 from .tensor import PointTensor, SparseTensor, cat
@@ -32,7 +33,7 @@ __version__ = "0.1.0"
 def install_as_torchsparse() -> None:
     """Register link_amd under the module names the reference imports (`torchsparse`,
     `torchsparse.nn`, `torchsparse.nn.functional`, `torchsparse.nn.utils`, `torchsparse.utils`,
-    `torchsparse.backend`) so that unmodified reference code such as
+    `torchsparse.utils.quantize`, `torchsparse.utils.collate`, `torchsparse.backend`) so that unmodified reference code such as
     `import torchsparse.nn.functional as F; from torchsparse import SparseTensor` resolves here."""
     import sys
     import types
@@ -47,8 +48,15 @@ def install_as_torchsparse() -> None:
     nn_mod.utils = nn_utils
     utils_mod = types.ModuleType("torchsparse.utils")
     utils_mod.make_ntuple = make_ntuple
+    quantize_mod = types.ModuleType("torchsparse.utils.quantize")
+    quantize_mod.sparse_quantize = sparse_quantize
+    collate_mod = types.ModuleType("torchsparse.utils.collate")
+    collate_mod.sparse_collate, collate_mod.sparse_collate_fn = sparse_collate, sparse_collate_fn
+    utils_mod.quantize, utils_mod.collate = quantize_mod, collate_mod
+    utils_mod.__path__ = []                                         # a package: `import torchsparse.utils.quantize` resolves
     ts.nn, ts.utils, ts.backend = nn_mod, utils_mod, backend
     ts.__version__ = "1.4.0+link_amd"
     sys.modules.update({"torchsparse": ts, "torchsparse.nn": nn_mod, "torchsparse.nn.functional": functional,
                         "torchsparse.nn.utils": nn_utils, "torchsparse.utils": utils_mod,
+                        "torchsparse.utils.quantize": quantize_mod, "torchsparse.utils.collate": collate_mod,
                         "torchsparse.backend": backend})

@@ -127,6 +127,13 @@ SEGLOSS_PRESENT, SEGLOSS_ALL = 0, 1                           # link_segloss_for
 SEGLOSS_MIN_CLASSES, SEGLOSS_MAX_CLASSES = 2, 32
 
 
+SEGQ_INT, SEGQ_ROUND = 0, 1                                   # link_seg_quantize::mode
+SEGQ_FLAG_EXTENT, SEGQ_FLAG_NONFINITE, SEGQ_FLAG_KEYBITS = 1, 2, 4
+SORT_TILE = 2048                                              # LINK_SEGQ_SORT_TILE: pairs per tile of the quantiser's radix sort
+SEGEVAL_ROWS, SEGEVAL_PREDICTIONS = 0, 1                      # link_seg_vote_eval::input_kind
+SEGEVAL_MAX_VOTES = 16
+
+
 CENTER_LOGITS, CENTER_PROBAS = 0, 1                           # link_center_loss_forward::input_kind
 CENTER_MAX_TASKS, CENTER_MAX_CLASSES, CENTER_MAX_OBJECTS, CENTER_MAX_SLOTS, CENTER_MAX_BATCH = 8, 16, 2048, 4096, 1024
 STRUCT_CENTER_ASSIGN_GEOM = 9                                 # its id for link_abi_struct_size
@@ -338,6 +345,12 @@ SIGNATURES = {
     "link_center_loss_forward": (c_int, [c_void_p] * 6 + [POINTER(c_int64), c_int32, c_int32] + [c_void_p] * 5 + [c_int32] * 5 + [POINTER(c_float), c_float, c_void_p,
                                          c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "link_center_loss_backward": (c_int, [c_void_p] * 5 + [c_int32] * 6 + [c_void_p] * 6 + [POINTER(c_int64), c_void_p]),
+    # section M: segmentation front end and validation -- quantise, vote, count (csrc/segio.hip)
+    "link_seg_quantize_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "link_seg_quantize": (c_int, [c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                  c_int64] + [c_void_p] * 5),
+    "link_seg_vote_eval": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int64] +
+                           [c_void_p] * 4),
 }
 
 _lib = None
