@@ -779,7 +779,13 @@ typedef struct {
   int32_t k2_lds_pad;  /* which workgroups share a CU when several frames are in flight */
   int32_t k1_form;     /* 0 = cell-range form (a wave owns a range of cells: LDS voxel list + X tile; the faster one with frames in
                           flight); 1 = tile form (id slots, in-wave id sort, per-cell sums by segmented DPP scan in the matrix-core
-                          accumulator layout; 36 KB of LDS, any cell size up to the slot capacity in one pass structure) */
+                          accumulator layout; 36 KB of LDS, any cell size up to the slot capacity in one pass structure); 2 = matrix-core
+                          sums form (C = 32 / 64).
+                          bit 4 (cell-range form): write the id-ordered records back to the slot lists in every cold call.  By default
+                          link_elk_core_dense_forward leaves that store out when its own insert filled the lists (build_index 1) and
+                          the quad-consumer gather kernel reads them (it takes a cell's records in any order; the pre_mix kernel orders
+                          them for itself in every call, warm ones included); rows are the same bit for bit, the bit is what the form
+                          without the store is tested and measured against.  link_dc_premix_modsum on its own always writes back */
   int32_t k2_form;     /* 0 = by measurement: producer / consumer form with quad consumers (two-part rows whose channels j and j + C/2
                           share theta), producer / consumer form with pair consumers (other two-part rows), own-cell form (cos_x, r = 3),
                           single-role form (cos_x, r = 2).  bit 3: pair consumers (the round-2 kernel) instead of quad consumers;

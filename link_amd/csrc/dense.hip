@@ -748,6 +748,8 @@ extern "C" int link_dc_demod(const float *A, const float *fin, const int32_t *co
                              void *stream);
 
 namespace link {
+int dc_premix_modsum_run(const link_dc_buffers_t *, const link_dc_grid_t *, const link_elk_desc_t *, int64_t, int32_t, bool, void *);
+bool dc_gather_demod_takes_quads(const link_dc_buffers_t *, const link_elk_desc_t *);
 int dc_index_ids_stats(const link_dc_buffers_t *, const link_dc_grid_t *, int64_t, int32_t *, hipStream_t);
 int dc_index_stats_run(const link_dc_buffers_t *, const link_dc_grid_t *, int64_t, int32_t *, hipStream_t);
 }  // namespace link
@@ -758,7 +760,7 @@ int dc_index_stats_run(const link_dc_buffers_t *, const link_dc_grid_t *, int64_
 extern "C" int link_dc_index_probe(const link_dc_buffers_t *b, const link_dc_grid_t *g, int64_t n, int32_t *stats, void *stream) {
   if (!b || !g || !stats || n < 0) return LINK_ERR_ARG;
   if (n == 0) return LINK_OK;
-  return b->tune.k1_form == 1 ? dc_index_ids_stats(b, g, n, stats, S(stream)) : dc_index_stats_run(b, g, n, stats, S(stream));
+  return (b->tune.k1_form & 15) == 1 ? dc_index_ids_stats(b, g, n, stats, S(stream)) : dc_index_stats_run(b, g, n, stats, S(stream));
 }
 
 extern "C" int link_elk_core_dense_forward(const link_dc_buffers_t *b, const link_dc_grid_t *g,
@@ -774,11 +776,16 @@ extern "C" int link_elk_core_dense_forward(const link_dc_buffers_t *b, const lin
   if (fused) {
     // index -> fused pre_mix + modulate + per-cell sum -> box gather -> per-voxel de-modulate
     if (build_index == 1) {                            // 2: link_dc_index_probe inserted this frame already
-      rc = b->tune.k1_form == 1 ? link_dc_index_ids(b->coords, n, g, b->cnt, b->sid, b->vcell, b->hdr, stream)
+      rc = (b->tune.k1_form & 15) == 1 ? link_dc_index_ids(b->coords, n, g, b->cnt, b->sid, b->vcell, b->hdr, stream)
                                 : link_dc_index(b->coords, n, g, b->cnt, b->slots, b->vcell, b->hdr, stream);
       if (rc != LINK_OK) return rc;
     }
-    rc = link_dc_premix_modsum(b, g, desc, n, build_index ? 0 : 1, stream);
+    // The id-ordered records go back to the slot lists unless this call's own insert stored them (build_index 1: a probed frame's
+    // lists, build_index 2, belong to the caller -- the block driver maps neighbours from them) and the quad-consumer kernel, which
+    // takes a cell's records in any order, reads them below.  A later warm call orders the records again for itself.
+    const bool quads = build_index == 1 && (mode & 4) && desc->c == 64 && (desc->r == 2 || desc->r == 3) &&
+                       link::dc_gather_demod_takes_quads(b, desc);
+    rc = link::dc_premix_modsum_run(b, g, desc, n, build_index ? 0 : 1, !quads, stream);
     if (rc != LINK_OK) return rc;
   } else {
     rc = link_dc_premix_insert(reinterpret_cast<const float *>(b->feats), b->coords, b->w_pre, b->pre_ln_w, b->pre_ln_b, n, desc->c, desc->eps, g,

@@ -13,7 +13,9 @@
 //   stream A   k_dc_batch_k1       PERSISTENT, one 4-wave workgroup per CU: stages W / LayerNorm / theta parameters ONCE, then every
 //                                  wave draws (frame, range of cells) items off its XCD's cursor: dc_k1_range (the body of the
 //                                  stand-alone kernel) reading the insert's counts / records with sc1 loads and publishing S rows /
-//                                  counts / sorted records with sc1 stores; one arrival on k1_done[frame] per item
+//                                  counts with sc1 stores (the records stay as the insert stored them: the quad consumers of the K2
+//                                  role take a cell's records in any order; -DDC_BT_K1_WRITEBACK=1 stores them back in id order);
+//                                  one arrival on k1_done[frame] per item
 //   stream B   k_dc_batch_k2       PERSISTENT, one 8-wave workgroup per CU: draws (frame, tile) items off its XCD's cursor (tiles of
 //                                  a frame keep the XCD they have in the stand-alone kernel: halo planes stay in one L2), ONE relaxed
 //                                  poll of k1_done[frame], then dc_k2q_body (the stand-alone kernel's body, every global read an sc1
@@ -22,7 +24,7 @@
 // No workgroup ever waits on a workgroup of its OWN kernel and every role draws its work off cursors, so whichever workgroups are
 // resident finish the batch: insert waits on nothing, K1 on insert arrivals, K2 on K1 arrivals; launch order = dependence order.
 // Co-residency is shaped, not required: LDS is handed out in 128 granules of 1 280 bytes per CU (tools/coresidency_probe.hip) -- K1
-// padded to 65, K2 63, so one of each fills a CU and two K1 workgroups do not fit; registers per SIMD 208 + 2 x 128 + 32 of 512
+// padded to 65, K2 63, so one of each fills a CU and two K1 workgroups do not fit; registers per SIMD 208 + 2 x 128 + 40 of 512 (204, 127 and 33 aligned up to multiples of 8)
 // (tests/test_cpu_abi.py::test_batch_kernels_resource_shape reads them off the built code object); the insert has no LDS at all.
 // Every spin is bounded (DC_BT_TIMEOUT_TICKS of the 100 MHz clock) and watches a shared error word: a violated assumption ends the
 // call with LINK_BATCH_TIMEOUT in link_dc_batch_status, not with a hung GPU.
@@ -30,7 +32,9 @@
 // Visibility inside the launches follows MI355X_MICROARCH.md "inter-workgroup visibility": producers store write-through (sc1)
 // and have their stores acknowledged (vmcnt) before their arrival atomic; consumers read with sc1 loads (served by the L2, never by
 // the CU's L1) -- no buffer_wbl2 / buffer_inv on the path.  The atomic counters of the insert (cnt) are device-scope atomics and live
-// at the memory side.
+// at the memory side.  The RECORDS K2 reads are the insert's own, one hop further back: the insert stores them write-through and has
+// them acknowledged before its arrival on ins_done[frame]; a K1 wave starts on a range of the frame only when it has seen ins_done
+// complete, and posts its arrival on k1_done[frame] after that; K2 polls k1_done complete and then reads the records with sc1 loads.
 //
 // Results: bit for bit those of link_elk_core_dense_forward per frame (same device bodies, same arithmetic; the launch
 // geometry -- cells per K1 item, z-segments of K2 -- does not enter any sum's order).  C = 64, cg = 32, cos / sin, r in {2, 3},

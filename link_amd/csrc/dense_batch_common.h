@@ -26,6 +26,11 @@
 #define DC_BT_RELEASE_FENCE 0       /* 1: K1 publishes with an agent-scope release fence (buffer_wbl2) in front of its arrival as well
                                        -- belt and braces for A/B; every published table is stored write-through already */
 #endif
+#ifndef DC_BT_K1_WRITEBACK
+#define DC_BT_K1_WRITEBACK 0        /* 1: the K1 role writes the id-ordered records back to the slot lists, as the stand-alone kernel does in front of
+                                       the pair-consumer gather kernels.  The K2 role runs the quad consumers, which take a cell's records in any order:
+                                       a scattered 16-byte write-through store per voxel that nothing reads (dense_k1_impl.h, dc_k1_range WB) */
+#endif
 
 namespace link {
 // sync words of one launch set (int32, zeroed before the launches): every counter on its own 64-byte line

@@ -27,12 +27,13 @@ int dc_tiles_modsum(const link_dc_buffers_t *b, const link_dc_grid_t *g, const l
 // the fp16 / bf16 instantiations live in their own translation units (dense_fused_f16.hip, dense_fused_bf16.hip)
 #define DC_DECL_IO(NS)                                                                                                    \
   namespace NS {                                                                                                           \
-  int run_premix_modsum(const link_dc_buffers_t *, const link_dc_grid_t &, const link_elk_desc_t &, int64_t, bool,        \
+  int run_premix_modsum(const link_dc_buffers_t *, const link_dc_grid_t &, const link_elk_desc_t &, int64_t, bool, bool,  \
                         hipStream_t);                                                                                      \
   int run_demod(const float *, const float *, const int32_t *, const int32_t *, const float *, const float *,             \
                 const float *, const float *, const link_elk_desc_t &, const link_dc_grid_t &, int64_t, void *,            \
                 hipStream_t);                                                                                              \
   int run_gather_demod(const link_dc_buffers_t *, const link_dc_grid_t &, const link_elk_desc_t &, int64_t, hipStream_t); \
+  bool gather_demod_takes_quads(const link_dc_buffers_t *, const link_elk_desc_t &);                                       \
   }
 DC_DECL_IO(dcio_f16)
 DC_DECL_IO(dcio_bf16)
@@ -386,8 +387,12 @@ static int dc_common_ok(const link_dc_buffers_t *b, const link_dc_grid_t *g, con
   return LINK_OK;
 }
 
-extern "C" int link_dc_premix_modsum(const link_dc_buffers_t *b, const link_dc_grid_t *g, const link_elk_desc_t *d,
-                                     int64_t n, int32_t warm, void *stream) {
+namespace link {
+// link_dc_premix_modsum with a say on the write-back of the id-ordered records (dense_k1_impl.h, dc_k1_range WB).  `writeback` false
+// is the inference forward's (link_elk_core_dense_forward) when the quad-consumer gather kernel follows on the same buffers; the
+// cell-range form honours it, the other forms of the kernel have no such store.
+int dc_premix_modsum_run(const link_dc_buffers_t *b, const link_dc_grid_t *g, const link_elk_desc_t *d, int64_t n, int32_t warm,
+                         bool writeback, void *stream) {
   if (dc_common_ok(b, g, d, n) != LINK_OK) return LINK_ERR_ARG;
   if (d->c != 16 && d->c != 32 && d->c != 64) return LINK_ERR_ARG;
   if (g->k > 352) return LINK_ERR_ARG;                 // a cell's records must fit the wave's LDS list (LCAP)
@@ -397,12 +402,28 @@ extern "C" int link_dc_premix_modsum(const link_dc_buffers_t *b, const link_dc_g
       !b->S || !b->hdr)
     return LINK_ERR_ARG;
   hipStream_t st = S(stream);
-  if (b->tune.k1_form == 1) return dc_tiles_modsum(b, g, d, n, warm != 0, st);
+  if ((b->tune.k1_form & 15) == 1) return dc_tiles_modsum(b, g, d, n, warm != 0, st);
+  const bool wb = writeback || (b->tune.k1_form & 16);   // bit 4: the write-back forced on (what the forms without it are tested against)
   switch (b->io_dtype) {
-    case 1: return dcio_f16::run_premix_modsum(b, *g, *d, n, warm != 0, st);
-    case 2: return dcio_bf16::run_premix_modsum(b, *g, *d, n, warm != 0, st);
-    default: return dcio_f32::run_premix_modsum(b, *g, *d, n, warm != 0, st);
+    case 1: return dcio_f16::run_premix_modsum(b, *g, *d, n, warm != 0, wb, st);
+    case 2: return dcio_bf16::run_premix_modsum(b, *g, *d, n, warm != 0, wb, st);
+    default: return dcio_f32::run_premix_modsum(b, *g, *d, n, warm != 0, wb, st);
   }
+}
+// does link_dc_gather_demod run the quad-consumer kernel on these buffers?
+bool dc_gather_demod_takes_quads(const link_dc_buffers_t *b, const link_elk_desc_t *d) {
+  if (!b || !d) return false;
+  switch (b->io_dtype) {
+    case 1: return dcio_f16::gather_demod_takes_quads(b, *d);
+    case 2: return dcio_bf16::gather_demod_takes_quads(b, *d);
+    default: return dcio_f32::gather_demod_takes_quads(b, *d);
+  }
+}
+}  // namespace link
+
+extern "C" int link_dc_premix_modsum(const link_dc_buffers_t *b, const link_dc_grid_t *g, const link_elk_desc_t *d,
+                                     int64_t n, int32_t warm, void *stream) {
+  return link::dc_premix_modsum_run(b, g, d, n, warm, true, stream);
 }
 
 extern "C" int link_dc_demod(const float *A, const float *fin, const int32_t *coords, const int32_t *vcell,

@@ -15,7 +15,7 @@ using namespace link;
 
 #include "dense_k1_impl.h"
 
-template <int C, int OP, int NB, bool PIPE>
+template <int C, int OP, int NB, bool PIPE, bool WB = true>
 static int launch_k1p(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
                      bool warm, hipStream_t st) {
   using K = dc_k1_cfg<C, OP>;
@@ -30,42 +30,47 @@ static int launch_k1p(const link_dc_buffers_t *b, const link_dc_grid_t &g, const
   // second one of its own kind shares it with the other frame's gather kernel instead -- the better mix (bench.py)
   const int lds_k1 = K::LDS_BYTES + k1_pad <= 160 * 1024 ? K::LDS_BYTES + k1_pad : K::LDS_BYTES;
   if (lds_k1 > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_modsum<C, OP, NB, PIPE>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_modsum<C, OP, NB, PIPE, WB>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds_k1);
-  hipLaunchKernelGGL((k_dc_premix_modsum<C, OP, NB, PIPE>), dim3((unsigned)wgs), dim3(64 * K::NW), lds_k1, st, b->feats,
+  hipLaunchKernelGGL((k_dc_premix_modsum<C, OP, NB, PIPE, WB>), dim3((unsigned)wgs), dim3(64 * K::NW), lds_k1, st, b->feats,
                      reinterpret_cast<int4 *>(b->slots), b->cnt, b->cell_n, b->w_pre, b->pre_ln_w, b->pre_ln_b,
                      b->w_pos, b->alpha, d.cg, d.coord_div, d.eps, n, g, cpw, warm, b->S, b->fin, b->hdr,
                      reinterpret_cast<unsigned long long *>(b->tune.k1_dbg));
   return check_launch("link_dc_premix_modsum");
 }
 
+// wb = false: the caller knows that the quad-consumer gather kernel reads this call's records (any order serves it) -- the kernel
+// without the write-back of the id-ordered records, built for what that kernel serves (C = 64, cg = 32, two-part rows)
 template <int C, int OP, int NB>
 static int launch_k1(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
-                     bool warm, hipStream_t st) {
+                     bool warm, bool wb, hipStream_t st) {
   // (the software-pipelined tile variant -- PIPE, 253 registers -- was re-measured in round 6 in the timed geometry, where its 256
   // registers do fit beside two gather waves: 35.7 against 34.2 us / frame; instantiations removed, docs/experiments.md section 6)
+  if constexpr (C == 64 && NB == 2 && OP != LINK_OP_COSX) {
+    if (!wb) return launch_k1p<C, OP, NB, false, false>(b, g, d, n, warm, st);
+  }
   return launch_k1p<C, OP, NB, false>(b, g, d, n, warm, st);
 }
 
 template <int C, int OP>
 static int dispatch_k1_nb(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
-                          bool warm, hipStream_t st) {
+                          bool warm, bool wb, hipStream_t st) {
   constexpr int T = C / 16;
   int nb = (d.cg % 16 == 0) ? d.cg / 16 : T;
   if (nb > T) nb = T;
-  if (nb == T) return launch_k1<C, OP, T>(b, g, d, n, warm, st);
-  if (T >= 2 && nb == T / 2) return launch_k1<C, OP, (T >= 2 ? T / 2 : 1)>(b, g, d, n, warm, st);
-  if (T >= 4 && nb == T / 4) return launch_k1<C, OP, (T >= 4 ? T / 4 : 1)>(b, g, d, n, warm, st);
-  return launch_k1<C, OP, T>(b, g, d, n, warm, st);    // any other grouping: every block evaluates its own theta
+  if (nb == T) return launch_k1<C, OP, T>(b, g, d, n, warm, wb, st);
+  if (T >= 2 && nb == T / 2) return launch_k1<C, OP, (T >= 2 ? T / 2 : 1)>(b, g, d, n, warm, wb, st);
+  if (T >= 4 && nb == T / 4) return launch_k1<C, OP, (T >= 4 ? T / 4 : 1)>(b, g, d, n, warm, wb, st);
+  return launch_k1<C, OP, T>(b, g, d, n, warm, wb, st);    // any other grouping: every block evaluates its own theta
 }
 
 template <int C>
 static int dispatch_k1_op(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
-                          bool warm, hipStream_t st) {
+                          bool warm, bool wb, hipStream_t st) {
   switch (d.op) {
-    case LINK_OP_COS: return dispatch_k1_nb<C, LINK_OP_COS>(b, g, d, n, warm, st);
-    case LINK_OP_SIN: return dispatch_k1_nb<C, LINK_OP_SIN>(b, g, d, n, warm, st);
-    default: return dispatch_k1_nb<C, LINK_OP_COSX>(b, g, d, n, warm, st);
+    case LINK_OP_COS: return dispatch_k1_nb<C, LINK_OP_COS>(b, g, d, n, warm, wb, st);
+    case LINK_OP_SIN: return dispatch_k1_nb<C, LINK_OP_SIN>(b, g, d, n, warm, wb, st);
+    default: return dispatch_k1_nb<C, LINK_OP_COSX>(b, g, d, n, warm, wb, st);
   }
 }
 
@@ -872,6 +877,17 @@ __global__ void __launch_bounds__(512, 4) k_dc_gather_demod_split(
 }
 
 
+// Does launch_k2 run the quad-consumer kernel on these buffers?  (Its own test, stated once: the pre_mix launcher leaves the
+// write-back of the id-ordered records out only in front of that kernel.)
+template <int OP, int R>
+static bool k2_takes_quads(const link_dc_buffers_t *b, const link_elk_desc_t &d) {
+  using K2 = dc_k2_cfg<OP, R>;
+  const bool pair = d.c == 2 * d.cg && (d.op == LINK_OP_COS || d.op == LINK_OP_SIN);
+  const bool own = (b->tune.k2_form & 4) || (!(b->tune.k2_form & 1) && !K2::SPLIT_FITS && R == 3);
+  if constexpr (dc_k2q_cfg<OP, R>::FITS) return !own && pair && !b->alpha && !(b->tune.k2_form & 9) && !(b->tune.k2_form & 2);
+  return false;
+}
+
 template <int OP, int R>
 static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
                      hipStream_t st) {
@@ -923,7 +939,7 @@ static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const 
     return check_launch("link_dc_gather_demod");
   }
   if constexpr (dc_k2q_cfg<OP, R>::FITS) {             // two-part rows, theta shared by channels j / j + 32: quad consumers (bit 3: round-2 pair form)
-    if (pair && !b->alpha && !(b->tune.k2_form & 9) && !k2_single) {
+    if (k2_takes_quads<OP, R>(b, d)) {
       using KQ = dc_k2q_cfg<OP, R>;
       // the quad form's own tile list: 1 x 10 / 10 x 1 strips on the rim of an axis of 4 m + 1 cells (k2_form bit 4: square rim tiles,
       // the launch of before -- what the strips are tested against bit for bit)
@@ -971,15 +987,15 @@ static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const 
 }
 
 int run_premix_modsum(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,
-                      bool warm, hipStream_t st) {
-  if (b->tune.k1_form == 2) {                          // matrix-core sums form (dense_fused_mm_impl.h): C = 32 / 64
+                      bool warm, bool wb, hipStream_t st) {
+  if ((b->tune.k1_form & 15) == 2) {                   // matrix-core sums form (dense_fused_mm_impl.h): C = 32 / 64
     if (d.c == 64) return dispatch_k1m_op<64>(b, g, d, n, warm, st);
     if (d.c == 32) return dispatch_k1m_op<32>(b, g, d, n, warm, st);
   }
   switch (d.c) {
-    case 16: return dispatch_k1_op<16>(b, g, d, n, warm, st);
-    case 32: return dispatch_k1_op<32>(b, g, d, n, warm, st);
-    default: return dispatch_k1_op<64>(b, g, d, n, warm, st);
+    case 16: return dispatch_k1_op<16>(b, g, d, n, warm, wb, st);
+    case 32: return dispatch_k1_op<32>(b, g, d, n, warm, wb, st);
+    default: return dispatch_k1_op<64>(b, g, d, n, warm, wb, st);
   }
 }
 
@@ -993,6 +1009,12 @@ int run_demod(const float *A, const float *fin, const int32_t *coords, const int
     default: launch_dc_demod<32>(d, n, g.vp + 1, st, A, fin, coords, vcell, w_pos, alpha, ln_w, ln_b, out); break;
   }
   return check_launch("link_dc_demod");
+}
+
+bool gather_demod_takes_quads(const link_dc_buffers_t *b, const link_elk_desc_t &d) {
+  if (d.c != 64 || (d.r != 2 && d.r != 3)) return false;
+  if (d.r == 3) return d.op == LINK_OP_COS ? k2_takes_quads<LINK_OP_COS, 3>(b, d) : (d.op == LINK_OP_SIN ? k2_takes_quads<LINK_OP_SIN, 3>(b, d) : false);
+  return d.op == LINK_OP_COS ? k2_takes_quads<LINK_OP_COS, 2>(b, d) : (d.op == LINK_OP_SIN ? k2_takes_quads<LINK_OP_SIN, 2>(b, d) : false);
 }
 
 int run_gather_demod(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,

@@ -9,7 +9,7 @@
 //   dc_k1_prefetch  the first chunk's cell ids, inline records and counts -- requested BEFORE the staging so the two latencies overlap
 //   dc_k1_range     one wave's range of cells [c_begin, c_end): counts -> wave prefix scan -> id-ordered voxel list in LDS -> tiles
 //                   of 16 voxels (row gather, contraction on the matrix cores, LayerNorm, theta / sincos / modulate, X tile -> LDS,
-//                   per-cell sums, one S row store per cell); publishes cell_n, zeroes cnt, writes the sorted records back
+//                   per-cell sums, one S row store per cell); publishes cell_n, zeroes cnt and -- WB -- writes the sorted records back
 #pragma once
 
 #ifndef DC_K1_LCAP
@@ -42,6 +42,11 @@
 #ifndef DC_K1_SWAP_SUMS
 #define DC_K1_SWAP_SUMS 1  /* LayerNorm statistics over a voxel's four lane groups through v_permlane32_swap / v_permlane16_swap (VALU) instead
                               of two ds_bpermute each: four dependent LDS round trips per tile leave the wave's chain (round 5) */
+#endif
+#ifndef DC_K1_LATE_PUBLISH
+#define DC_K1_LATE_PUBLISH 0 /* dc_k1_range, 1: a chunk's publishing stores (cell_n, cnt, kept write-back, zero rows) are issued BEHIND the row
+                                requests of its first two tiles, and the first tile's wait leaves them in flight; 0: in front of them, where that
+                                wait covers their acknowledgements.  Measured neutral (docs/experiments.md section 9): off */
 #endif
 // v + v[lane ^ 16] + v[lane ^ 32] + v[lane ^ 48]
 __device__ __forceinline__ float dc_k1_sum_groups(float v) {
@@ -186,7 +191,12 @@ __device__ __forceinline__ void dc_k1_stage(char *smem_raw, const float *__restr
 
 // One wave's range of cells.  pc_f .. rf3: what dc_k1_prefetch requested for the range's first chunk; w_big / th_slow: the
 // workgroup-uniform verdicts of the staging; wid: the wave's number in the launch (profiling rows only).
-template <int C, int OP, int NB, bool PIPE, bool COH = false>
+// WB: the id-ordered records go back to the slot list.  The order is this function's own need (its per-cell sums run in id order, and it
+// orders the records of every call, warm ones included); of the gather kernels only the pair consumers walk a cell's list, and they must
+// pair the same voxels in every run (rank order from the insert's atomics is not reproducible).  The quad-consumer kernel handles one
+// (cell, slot) per quad -- record, theta, row rec.w -- and takes the records in any order: in front of it the write-back is a scattered
+// 16-byte store per voxel that nothing reads (WB = false: the batch K1 role, and the inference forward where that kernel follows).
+template <int C, int OP, int NB, bool PIPE, bool COH = false, bool WB = true>
 __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restrict__ feats, int4 *__restrict__ slots,
                                             uint32_t *__restrict__ cnt, int32_t *__restrict__ cell_n,
                                             const float *__restrict__ w_pre, float coord_div, float eps, int64_t n,
@@ -247,6 +257,7 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
     const unsigned long long fit = __ballot(lane < nrem && incl <= LCAPX);
     const int nfit = __builtin_amdgcn_readfirstlane(__popcll(fit));      // >= 1: a cell never exceeds LCAP
     const int Ttot = __builtin_amdgcn_readlane(incl, nfit - 1);
+    int4 rs[4] = {r0, r1, r2, r3};                      // the inline records in id order (cell lanes)
     if (lane < nfit) {
       const int excl = incl - nv;
       // order the inline records by voxel id: keys id*4+slot through a 5-exchange network
@@ -268,9 +279,7 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
         r.z = s == 0 ? r0.z : (s == 1 ? r1.z : (s == 2 ? r2.z : r3.z));
         r.w = ks[j] >> 2;
         if (j < nv) { list[excl + j] = r; scell[excl + j] = pc; }
-        // the id-ordered records go back to the slot list: the fused gather+demod walks it and must pair the
-        // same voxels in every run (rank order from the atomics is not reproducible)
-        st16i_c<COH>(r_slots, (j < nv && nv <= DC_INL && !warm) ? ((uint32_t)pc * DC_INL + j) * 16u : DC_OOB, r);
+        rs[j] = r;
       }
       for (int k = DC_INL; k < nv; k++) {               // overflow records: insertion by id (rare)
         const int4 r = ld16i_c<COH>(r_slots, slots, dc_slot(g, pc, k));
@@ -282,18 +291,34 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
         }
         list[excl + pos] = r;
       }
-      if (nv > DC_INL && !warm)
-        for (int k = 0; k < nv; k++) st16i_c<COH>(r_slots, dc_slot(g, pc, k) * 16u, list[excl + k]);
+      if constexpr (WB) {                               // an overflow cell is rewritten whole (rare, and a data-dependent number of stores:
+        if (nv > DC_INL && !warm)                       // it stays in front of the row requests)
+          for (int k = 0; k < nv; k++) st16i_c<COH>(r_slots, dc_slot(g, pc, k) * 16u, list[excl + k]);
+      }
     }
-    {                                                   // publish the counts, reset the counters
-      const uint32_t coff = (lane < nfit && !warm) ? (uint32_t)pc * 4u : DC_OOB;
+    // What the chunk publishes.  A FIXED number of stores per lane -- the counts, the counter reset and (WB) the four inline records
+    // in id order -- so that, issued behind the row requests of the first two tiles (DC_K1_LATE_PUBLISH), the first tile's wait comes
+    // out as a counted vmcnt that leaves them in flight: memory operations retire in issue order, and in front of the requests that
+    // wait takes in the acknowledgement of every write-through store of the chunk.  The zero rows of empty cells are a data-dependent
+    // number of stores: they then follow the first tile's matrix instructions, behind that wait.  (Measured neutral once the write-back
+    // is gone -- two stores per lane and chunk are left to move: docs/experiments.md section 9.)
+    auto publish = [&]() {
+      if constexpr (WB) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          st16i_c<COH>(r_slots, (lane < nfit && j < nv && nv <= DC_INL && !warm) ? ((uint32_t)pc * DC_INL + j) * 16u : DC_OOB, rs[j]);
+      }
+      const uint32_t coff = (lane < nfit && !warm) ? (uint32_t)pc * 4u : DC_OOB;                          // publish the counts, reset the counters
       st4i_c<COH>(r_n, coff, nv);
       st4i(r_cnt, coff, 0);
-    }
-    for (unsigned long long em = __ballot(lane < nfit && nv == 0); em; em &= em - 1) {   // empty cells: zero rows
-      const int pcj = __builtin_amdgcn_readlane(pc, __builtin_ctzll(em));
-      st16(r_S, ract ? (uint32_t)pcj * (uint32_t)K::RB + (uint32_t)rl * 16u : DC_OOB, make_float4(0.f, 0.f, 0.f, 0.f));
-    }
+    };
+    auto publish_empty = [&]() {
+      for (unsigned long long em = __ballot(lane < nfit && nv == 0); em; em &= em - 1) {   // empty cells: zero rows
+        const int pcj = __builtin_amdgcn_readlane(pc, __builtin_ctzll(em));
+        st16(r_S, ract ? (uint32_t)pcj * (uint32_t)K::RB + (uint32_t)rl * 16u : DC_OOB, make_float4(0.f, 0.f, 0.f, 0.f));
+      }
+    };
+    if constexpr (!DC_K1_LATE_PUBLISH) { publish(); publish_empty(); }
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (dbg) { const unsigned long long tqb = DC_NOW(); tq_cell += tqb - tqa; tqa = tqb; }
@@ -400,11 +425,18 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
     int4 recA = make_int4(0, 0, 0, 0), recB = recA, recC = recA;
     float4 fA[T], fB[T];
     floatx4 acA[T], acB[T];
-    if (PIPE && ntile > 0) {                            // pipeline fill: tile 0 multiplied, tile 1 requested
-      ld_rows(0, recA, fB);
-      ld_rows(ntile > 1 ? 1 : 0, recB, fA);
-      mfma_tile(fB, acA);
+    // The first two tiles are requested and the first one multiplied in front of the loop, in straight-line code: the only wait of a
+    // chunk that could cover the publishing stores is then one the compiler counts exactly (rows of tile 1 + the fixed stores stay in
+    // flight).  A chunk of one tile requests that tile twice.  PIPE: rows of tile 0 in fB, of tile 1 in fA (see the loop below).
+    if (ntile > 0) {
+      ld_rows(0, recA, PIPE ? fB : fA);
+      ld_rows(ntile > 1 ? 1 : 0, recB, PIPE ? fA : fB);
+      if constexpr (DC_K1_LATE_PUBLISH) publish();
+      mfma_tile(PIPE ? fB : fA, acA);
+    } else {                                            // nothing but empty cells
+      if constexpr (DC_K1_LATE_PUBLISH) publish();
     }
+    if constexpr (DC_K1_LATE_PUBLISH) publish_empty();
     if (dbg) { const unsigned long long tqb = DC_NOW(); tq_fill += tqb - tqa; tqa = tqb; }
     // step t: finishes tile t (record rec, accumulators ac), multiplies tile t+1 (record recn, rows fn) into
     // acn, requests tile t+2 (record rec2, rows f2)
@@ -558,10 +590,11 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
       // plain tiles: rows of tile t in fA (even t) / fB (odd t), the other set receives tile t+1 meanwhile
       using body_only = std::integral_constant<int, 1>;
       using sums_only = std::integral_constant<int, 2>;
-      if (ntile > 0) ld_rows(0, recA, fA);
       for (int t = 0; t < nloop; t += 2) {
-        if (t + 1 < ntile) ld_rows(t + 1, recB, fB);
-        mfma_tile(fA, acA);
+        if (t > 0) {                                    // (tile 0 was multiplied, tile 1 requested above)
+          if (t + 1 < ntile) ld_rows(t + 1, recB, fB);
+          mfma_tile(fA, acA);
+        }
         if (t > 0) step(sums_only{}, t - 1, recB, recB, recC, fB, fB, acA, acB);
         step(body_only{}, t, recA, recB, recC, fB, fB, acA, acB);
         if (t + 1 < nloop) {
@@ -582,7 +615,7 @@ __device__ __forceinline__ void dc_k1_range(char *smem_raw, const void *__restri
   }
 }
 
-template <int C, int OP, int NB, bool PIPE>
+template <int C, int OP, int NB, bool PIPE, bool WB = true>
 __global__ void __launch_bounds__(64 * DC_K1_NW, PIPE ? 2 : DC_K1_WAVES) k_dc_premix_modsum(
     const void *__restrict__ feats, int4 *__restrict__ slots, uint32_t *__restrict__ cnt,
     int32_t *__restrict__ cell_n, const float *__restrict__ w_pre, const float *__restrict__ ln_w,
@@ -614,6 +647,6 @@ __global__ void __launch_bounds__(64 * DC_K1_NW, PIPE ? 2 : DC_K1_WAVES) k_dc_pr
   const bool th_slow = DC_THETA_BOUND ? __syncthreads_or(th_big) != 0 : false;     // workgroup-uniform (the same in every workgroup)
   if (dbg) tq1 = DC_NOW();
   if (c_begin >= c_end) return;
-  dc_k1_range<C, OP, NB, PIPE>(smem_raw, feats, slots, cnt, cell_n, w_pre, coord_div, eps, n, g, warm, S_, fin, dbg, c_begin,
+  dc_k1_range<C, OP, NB, PIPE, false, WB>(smem_raw, feats, slots, cnt, cell_n, w_pre, coord_div, eps, n, g, warm, S_, fin, dbg, c_begin,
                                        c_end, pc_f, nv_f, rf0, rf1, rf2, rf3, w_big, th_slow, wid, tq0, tq1);
 }
