@@ -40,6 +40,9 @@ __global__ void __launch_bounds__(320, 3) k_dc_gather_demod_own(
     const float *__restrict__ fin, const float *__restrict__ w_pos, const float *__restrict__ alpha,
     const float *__restrict__ ln_w, const float *__restrict__ ln_b, int cg, float coord_div, float eps, int64_t n,
     link_dc_grid_t g, int txn, int tyn, int zsplit, int nwg, void *__restrict__ out, unsigned long long *__restrict__ dbg) {
+  // No implicit fusing of a * b + c in this body (the explicit fmaf stay): the two voxel slots of a pair, and the copies the compiler
+  // makes of the pair loop's body, must round alike -- see the de-modulation below
+#pragma clang fp contract(off)
   using KO = dc_k2o_cfg<OP, R>;
   unsigned long long tq0 = dbg ? __builtin_amdgcn_s_memtime() : 0, tq_bar = 0, tq_box = 0, tq_pairs = 0, tq_dma = 0;
   int tq_rounds = 0;
@@ -266,12 +269,17 @@ __global__ void __launch_bounds__(320, 3) k_dc_gather_demod_own(
 #pragma unroll
         for (int e = 0; e < 4; e++) {
           const float A0 = Av[0][e], A1 = Av[1][e];
+          // Both products ROUNDED (link_mul_rn): __fmul_rn / __fadd_rn are plain * and + to this compiler (inlined from a header, so
+          // the pragma above does not reach them), and of p + q it may fuse either product into the sum -- not the same one in the two
+          // slots of a pair or in two copies of this loop's body.  With that and the fused LayerNorm statistics below, a voxel's row
+          // depended on its rank in the cell's list by 1 - 4 ulp under cos_x wherever the records are not in id order (the unfused
+          // insert: tests/test_gpu_dense_lattice.py, slot capacity 512); rounding the products alone did not remove it, the pragma did
           if (OP == LINK_OP_SIN) {                                                   // linkunet.py:148
-            nvA[e] = __fsub_rn(__fmul_rn(A0, csA[e]), __fmul_rn(A1, snA[e]));
-            nvB[e] = __fsub_rn(__fmul_rn(A0, csB[e]), __fmul_rn(A1, snB[e]));
+            nvA[e] = __fsub_rn(link_mul_rn(A0, csA[e]), link_mul_rn(A1, snA[e]));
+            nvB[e] = __fsub_rn(link_mul_rn(A0, csB[e]), link_mul_rn(A1, snB[e]));
           } else {                                                                   // :162
-            nvA[e] = __fadd_rn(__fmul_rn(A0, csA[e]), __fmul_rn(A1, snA[e]));
-            nvB[e] = __fadd_rn(__fmul_rn(A0, csB[e]), __fmul_rn(A1, snB[e]));
+            nvA[e] = __fadd_rn(link_mul_rn(A0, csA[e]), link_mul_rn(A1, snA[e]));
+            nvB[e] = __fadd_rn(link_mul_rn(A0, csB[e]), link_mul_rn(A1, snB[e]));
           }
           if (OP == LINK_OP_COSX) {                                                  // :176
             nvA[e] = __fadd_rn(nvA[e], __fsub_rn(Av[P - 1][e], link_mul_rn(fxa[e], thA[e])));

@@ -532,9 +532,11 @@ class ElkCoreBatch:
     under the gather role of the first.  `check()` raises if a voxel was dropped or a kernel's bounded wait gave up."""
 
     def __init__(self, frames: int, n_cap: int, c: int, baseop: str, cg: int, r: int, s: int, bounds, device, eps: float = 1e-6,
-                 slot_cap: int = 0, share: Optional["ElkCoreBatch"] = None):
+                 slot_cap: int = 0, share: Optional["ElkCoreBatch"] = None, coord_div: float = 1.0):
         if c != 64 or cg != 32 or baseop not in ("cos", "sin") or r not in (2, 3):
             raise L.LinkAmdError("ElkCoreBatch: C = 64, cg = 32, cos / sin, r in {2, 3} (include/link_amd.h section H)")
+        if float(coord_div) != 1.0:
+            raise L.LinkAmdError("ElkCoreBatch: coord_div = 1 only (run such frames through ElkCorePlan)")
         if frames < 1:
             raise ValueError("ElkCoreBatch: at least one frame")
         self.plans = [ElkCorePlan(n_cap, c, baseop, cg, r, s, bounds, device, eps=eps, layout="dense", slot_cap=slot_cap)

@@ -13,6 +13,9 @@ and the final LayerNorm -- with plain torch ops on any device, in chunks of voxe
 
 Memory is O(chunk + blocks): no n-row float64 matrix ever exists.  `dtype=torch.float32` evaluates the same formula in fp32 (what
 fp32 evaluation costs against the float64 truth: `o32`).  Test infrastructure only: does not import link_amd."""
+import json
+import os
+
 import torch
 import torch.nn.functional as TF
 
@@ -152,3 +155,73 @@ class Ref64:
         """max|other - ref| / max|ref|, and whether `other` is finite everywhere."""
         d, m, ok = self.compare(other)
         return d / max(m, 1e-300), ok
+
+
+class Rounded:
+    """The float64 truth rounded to a half row type: what storing the result in that type alone costs."""
+
+    def __init__(self, ref, dt):
+        self.ref, self.dt = ref, dt
+
+    def rows(self, lo, hi):
+        return self.ref.rows(lo, hi).to(self.dt)
+
+
+def record_row(row, name="dense_parity.jsonl"):
+    """Append one case's row to `name` in the directory LINK_AMD_PARITY_DIR names; nothing is written when it is unset."""
+    d = os.environ.get("LINK_AMD_PARITY_DIR")
+    if not d:
+        return
+    try:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, name), "a") as f:
+            f.write(json.dumps(row) + "\n")
+    except OSError:
+        pass
+
+
+def gate_rows(case, ref, o32, out, dt=torch.float32, absolute=True, record=None):
+    """The float64 gate of one frame's rows `out` against `ref` (a Ref64 of the frame):
+      (a) every row finite -- the callers' result buffers start as NaN, so a row that was never written cannot pass;
+      (b) rel64 = max|out - ref| / max|ref| < 1e-4 for fp32 rows, 4e-3 for fp16, 3e-2 for bf16 (the result is rounded to the row
+          type at the kernel boundary) -- dropped with absolute=False, for frames whose theta is so large that evaluating the
+          formula itself in fp32 costs more than 1e-4 (tests/test_gpu_train_gate.py gates the same way);
+      (c) rel64 <= 4 * o32 + 2 * o_round + 2e-6, o32 = what evaluating the same formula in fp32 costs against the float64 truth,
+          o_round = what rounding the truth to the row type costs: an error that passes (b) but sits far above fp32 evaluation
+          still fails.
+    Nothing in a bound comes from the kernels under test.  `case`: a dict of the case's fields, or any label (kept under "case").
+    `record`: None, True (the row goes to dense_parity.jsonl, record_row) or a callable taking the row -- written BEFORE the
+    verdicts, so a failing case still leaves its figures.  Returns the row."""
+    rel64, finite = ref.rel(out)
+    o_round = 0.0 if dt == torch.float32 else ref.rel(Rounded(ref, dt))[0]
+    row = dict(case) if isinstance(case, dict) else dict(case=case)
+    row.update(n=int(ref.n), rel64=rel64, o32=o32, o_round=o_round)
+    if record is True:
+        record_row(row)
+    elif record is not None:
+        record(row)
+    assert finite, row
+    if absolute:
+        assert rel64 < (1e-4 if dt == torch.float32 else (4e-3 if dt == torch.float16 else 3e-2)), row
+    assert rel64 <= 4.0 * o32 + 2.0 * o_round + 2e-6, row
+    return row
+
+
+def gate_zero_rows(case, ref, ref32, out, scale, record=None):
+    """The gate for a frame whose rows are analytically ZERO before the final LayerNorm (sin on a voxel alone in its neighbourhood:
+    f sin cos - f cos sin), so that max|ref| is rounding residue and a relative error means nothing.  As tests/grad64.py, gate_zero:
+    what the kernels leave is held against the residue of the reference's own fp32 evaluation `ref32` (a Ref64 of the frame with
+    dtype=torch.float32): max|out - ref| <= 4 max|ref32 - ref| + 2e-6 `scale` (the size rows have when they are not zero: the norm
+    weights), with the float64 rows themselves below 1e-9 `scale`.  fp32 rows only."""
+    e, m64, finite = ref.compare(out)
+    o32 = ref.compare(ref32)[0]
+    row = dict(case) if isinstance(case, dict) else dict(case=case)
+    row.update(n=int(ref.n), zero=True, e=e, o32=o32, max_ref=m64, bound=4.0 * o32 + 2e-6 * scale)
+    if record is True:
+        record_row(row)
+    elif record is not None:
+        record(row)
+    assert finite and out.dtype == torch.float32, row
+    assert m64 <= 1e-9 * scale, row
+    assert e <= row["bound"], row
+    return row

@@ -31,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from tests.ref64 import Ref64  # noqa: E402
+from tests.ref64 import Ref64, gate_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -103,25 +103,6 @@ def _ref(kind, seed, dt, baseop, r):
     return ref, o32
 
 
-class _Rounded:
-    """The float64 truth rounded to a half row type: what storing the result in that type alone costs."""
-
-    def __init__(self, ref, dt):
-        self.ref, self.dt = ref, dt
-
-    def rows(self, lo, hi):
-        return self.ref.rows(lo, hi).to(self.dt)
-
-
-def _gate(case, ref, o32, out, dt):
-    rel64, finite = ref.rel(out)
-    o_round = 0.0 if dt == torch.float32 else ref.rel(_Rounded(ref, dt))[0]
-    row = dict(case=case, n=int(ref.n), rel64=rel64, o32=o32, o_round=o_round)
-    assert finite, row
-    assert rel64 < (1e-4 if dt == torch.float32 else 4e-3), row
-    assert rel64 <= 4.0 * o32 + 2.0 * o_round + 2e-6, row
-
-
 def _reverse_cell_lists(plan):
     """Reverse every cell's records in the plan's slot lists (inline region: DC_INL records per cell; overflow region behind it:
     k - DC_INL per cell -- csrc/dense_common.h, dc_slot)."""
@@ -189,4 +170,4 @@ def test_rows_without_the_record_write_back(kind, r, baseop, dt):
     assert torch.equal(first[0], first[2])                             # the repeated frame
     for i, sd in enumerate(seeds[:2]):
         ref, o32 = _ref(kind, sd, dt, baseop, r)
-        _gate((kind, r, baseop, str(dt), i), ref, o32, first[i], dt)                                    # 4.
+        gate_rows((kind, r, baseop, str(dt), i), ref, o32, first[i], dt)                                   # 4.

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from tests.helpers import s_uniform  # noqa: E402
-from tests.ref64 import Ref64  # noqa: E402
+from tests.ref64 import Ref64, gate_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BOUNDS = ((0, 0, 0, 0), (255, 255, 255, 0))
@@ -62,16 +62,6 @@ def _refs(feats, coords, blk, s, r):
     return ref, o32
 
 
-class _Rounded:
-    """The float64 truth rounded to a half row type: what storing the result in that type alone costs."""
-
-    def __init__(self, ref, dt):
-        self.ref, self.dt = ref, dt
-
-    def rows(self, lo, hi):
-        return self.ref.rows(lo, hi).to(self.dt)
-
-
 def _record(row):
     """Append one case's row to $LINK_AMD_PARITY_DIR/size_parity.jsonl (written before the case's verdicts: a failing case still
     leaves its numbers)."""
@@ -87,17 +77,9 @@ def _record(row):
 
 
 def _gate(case, ref, o32, out, dt=torch.float32):
-    """(a) - (c) of the module docstring for one frame's rows; the row goes to size_parity.jsonl before the verdicts."""
-    rel64, finite = ref.rel(out)
-    o_round = 0.0 if dt == torch.float32 else ref.rel(_Rounded(ref, dt))[0]
-    row = dict(case, n=int(ref.n), rel64=rel64, o32=o32, **({"o_round": o_round} if o_round else {}),
-               peak_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
-    _record(row)
-    assert finite, row
-    # half rows: the result is rounded to the row type at the kernel boundary -- the half gates of tests/test_gpu_batch.py
-    tol = TOL if dt == torch.float32 else (4e-3 if dt == torch.float16 else 3e-2)
-    assert rel64 < tol, row
-    assert rel64 <= 4.0 * o32 + 2.0 * o_round + 2e-6, row
+    """(a) - (c) of the module docstring for one frame's rows (tests/ref64.py, gate_rows); the row goes to size_parity.jsonl
+    before the verdicts."""
+    gate_rows(dict(case, peak_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)), ref, o32, out, dt, record=_record)
 
 
 def _free():
