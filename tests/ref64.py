@@ -180,7 +180,7 @@ def record_row(row, name="dense_parity.jsonl"):
         pass
 
 
-def gate_rows(case, ref, o32, out, dt=torch.float32, absolute=True, record=None):
+def gate_rows(case, ref, o32, out, dt=torch.float32, absolute=True, record=None, o_round=None):
     """The float64 gate of one frame's rows `out` against `ref` (a Ref64 of the frame):
       (a) every row finite -- the callers' result buffers start as NaN, so a row that was never written cannot pass;
       (b) rel64 = max|out - ref| / max|ref| < 1e-4 for fp32 rows, 4e-3 for fp16, 3e-2 for bf16 (the result is rounded to the row
@@ -191,9 +191,12 @@ def gate_rows(case, ref, o32, out, dt=torch.float32, absolute=True, record=None)
           still fails.
     Nothing in a bound comes from the kernels under test.  `case`: a dict of the case's fields, or any label (kept under "case").
     `record`: None, True (the row goes to dense_parity.jsonl, record_row) or a callable taking the row -- written BEFORE the
-    verdicts, so a failing case still leaves its figures.  Returns the row."""
+    verdicts, so a failing case still leaves its figures.  `o_round`: None, or the caller's own reference-side measurement of what
+    the contract's roundings cost (a contract that rounds more than once: tests/conv64.py).  `ref`: a Ref64, or anything with its
+    n, rows() and rel() (tests/conv64.py: Conv64).  Returns the row."""
     rel64, finite = ref.rel(out)
-    o_round = 0.0 if dt == torch.float32 else ref.rel(Rounded(ref, dt))[0]
+    if o_round is None:
+        o_round = 0.0 if dt == torch.float32 else ref.rel(Rounded(ref, dt))[0]
     row = dict(case) if isinstance(case, dict) else dict(case=case)
     row.update(n=int(ref.n), rel64=rel64, o32=o32, o_round=o_round)
     if record is True:
