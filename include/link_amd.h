@@ -1374,6 +1374,53 @@ int link_seg_vote_eval(const void *rows, int32_t io_dtype, int32_t input_kind, i
                        const int64_t *labels /* nullable */, int64_t ignore_label, const int32_t *lut /* [c], nullable */,
                        int32_t *pred /* [n_points], nullable */, int64_t *counters /* [3, c] */, void *stream);
 
+/* =============================================================================================
+ * N. CenterHead test-time augmentation (csrc/dettta.hip): the four flipped views, the fused decode of their maps, class-wise NMS
+ *
+ * What the reference does for its reported nuScenes results (configs/nusc/voxelnet/..._elkv3_flip.py and ..._flip_rot.py:
+ * double_flip=True, tt_rotation): on the host per frame, datasets/pipelines/test_aug.py:12-32 (three flipped copies of the cloud)
+ * after preprocess.py:153-156 (the rotation, core/bbox/box_np_ops.py:182-204); on the device in about forty torch ops per task,
+ * models/bbox_heads/center_head.py:320-421 (the maps of views 1-3 flipped back in place, sigmoid / exp, the mean of the four
+ * views) and :461-467 (the masks); on the host again :489-503 (the kept boxes rotated back); and detection/nms_better2.py:266-297
+ * (the passes of several angles merged: one rotate_nms_pcdet per class with that class's threshold, then the 500 best).
+ * Additive entries: the ABI version does not move.  All fp32, no atomics, no allocation, no host round trip; every entry takes a
+ * stream, keeps no state and is bitwise reproducible.
+ *
+ * link_tta_views: points float[n, ndim] = `batch` clouds one after the other, point_offsets int32[batch + 1] (device; [0] = 0,
+ *   ascending, [batch] = n).  out float[4 n, ndim] = the 4 batch clouds frame-major, view-minor: view v of cloud b occupies the
+ *   n_b rows from 4 point_offsets[b] + v n_b; out_offsets int32[4 batch + 1] (device) names them.  View 0 is the cloud with
+ *   columns 0, 1 rotated: x' = x cos_a + y sin_a, y' = x (-sin_a) + y cos_a, each product and sum rounded on its own (cos_a,
+ *   sin_a: the caller's float64 cos / sin of tt_rotation rounded to fp32, as the reference's matrix holds them); view 1 has
+ *   y = -y, view 2 x = -x, view 3 both; columns 2.. are copied.  cos_a == 1 and sin_a == 0: no arithmetic, bit for bit copies.
+ *   One launch.  Offsets that do not describe n rows write nothing for the clouds concerned (never out of bounds).
+ *   LINK_ERR_ARG: batch outside 1..16383, n outside [0, 2^29), ndim outside 3..16, cos_a / sin_a not finite, null pointers.
+ *
+ * link_center_decode_flip4: link_center_decode for maps of batch 4 frames in that order, read in place: cell (h, w) of a frame
+ *   reads view 1 at (h_size-1-h, w), view 2 at (h, w_size-1-w), view 3 at both.  Per view first: sigmoid of hm, exp of dim,
+ *   1 - reg_y in view 1, 1 - reg_x in view 2, both in view 3, rot's cos negated in view 1, its sin in view 2, both in view 3, vel's
+ *   y negated in view 1, its x in view 2, both in view 3; then the mean of the four views as ((v0 + v1) + v2) + v3) / 4; then as
+ *   link_center_decode (arg max of the mean scores, lowest class among equals; atan2f of the mean sin and cos; box assembly; the
+ *   masks).  Outputs as link_center_decode with batch = frames.  LINK_ERR_ARG as link_center_decode, with 4 frames > 65535.
+ *
+ * link_nms_mask_classwise: link_nms_mask's words (same layout, same n_dev convention; link_nms_reduce consumes them) for the
+ *   predicate labels[i] == labels[j] and rotated IoU > thr[labels[i]].  labels int32[cap], thr float[num_cls] (device).  A label
+ *   outside [0, num_cls) neither suppresses nor is suppressed.  A 64 x 64 tile without a common class costs no IoU work.
+ *
+ * link_tta_rotate_back: out float[m, ncol] (ncol 7, or 9 with the velocity pair in columns 6, 7) = boxes[idx[j]] (idx int64[m],
+ *   device; NULL: row j; then m <= n_src is the caller's business only in that rows past n_src are zeros) with columns 0, 1 and
+ *   6, 7 rotated as above by (cos_a, sin_a) and `angle` added to the last column -- center_head.py:489-503 with cos_a, sin_a,
+ *   angle of -tt_rotation.  angle == 0: a plain gather.  idx[j] < 0 or >= n_src: a row of zeros.  out must not overlap boxes.
+ * ============================================================================================= */
+int link_tta_views(const float *points, const int32_t *point_offsets /* [batch + 1], device */, int32_t batch, int64_t n, int32_t ndim,
+                   float cos_a, float sin_a, float *out /* [4 n, ndim] */, int32_t *out_offsets /* [4 batch + 1], device */, void *stream);
+int link_center_decode_flip4(const float *hm, const float *reg, const float *height, const float *dim, const float *rot, const float *vel,
+                             int32_t frames, int32_t num_cls, int32_t h, int32_t w, const link_center_geom_t *geom /* host */, float *boxes,
+                             int32_t *labels, float *scores, int32_t *counts, void *stream);
+int link_nms_mask_classwise(const float *boxes, const int32_t *labels, int64_t cap, const int32_t *n_dev, const float *thr /* [num_cls] */,
+                            int32_t num_cls, uint64_t *mask, void *stream);
+int link_tta_rotate_back(const float *boxes, int64_t n_src, int32_t ncol, const int64_t *idx /* [m], nullable */, int64_t m, float cos_a,
+                         float sin_a, float angle, float *out /* [m, ncol] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

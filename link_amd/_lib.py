@@ -351,6 +351,11 @@ SIGNATURES = {
                                   c_int64] + [c_void_p] * 5),
     "link_seg_vote_eval": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int64] +
                            [c_void_p] * 4),
+    # section N: CenterHead test-time augmentation -- views, fused decode, class-wise NMS mask, rotation back (csrc/dettta.hip)
+    "link_tta_views": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "link_center_decode_flip4": (c_int, [c_void_p] * 6 + [c_int32] * 4 + [POINTER(LinkCenterGeom)] + [c_void_p] * 5),
+    "link_nms_mask_classwise": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "link_tta_rotate_back": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None
