@@ -1257,6 +1257,8 @@ class Conv3d(nn.Module):
         if table is None:                               # 1x1x1: a dense GEMM on the rows
             out = torch.addcmul(shift, feats.float().matmul(self.kernel.detach()), scale)
             out = torch.relu_(out) if relu else out
+            if feats.dtype in (torch.float16, torch.bfloat16):        # 16-bit rows come back in the row type, as from the table branch
+                out = out.to(feats.dtype)
         else:
             kernel = self.kernel if self.kernel.ndim == 3 else self.kernel.unsqueeze(0)
             out = subm_conv_ln_add_relu(feats, kernel, table, order, scale, shift, 0.0, None, relu=relu, affine=True)
