@@ -1421,6 +1421,109 @@ int link_nms_mask_classwise(const float *boxes, const int32_t *labels, int64_t c
 int link_tta_rotate_back(const float *boxes, int64_t n_src, int32_t ncol, const int64_t *idx /* [m], nullable */, int64_t m, float cos_a,
                          float sin_a, float angle, float *out /* [m, ncol] */, void *stream);
 
+/* =============================================================================================
+ * O. Two-stage ROI head (csrc/roihead.hip): BEV features of the proposals, target assignment, loss, box refinement
+ *
+ * What the reference's TwoStageDetector does behind its first stage (detection/det3d/models/detectors/two_stage.py,
+ * models/second_stage/bird_eye_view.py, models/roi_heads/roi_head.py and roi_head_template.py,
+ * models/roi_heads/target_assigner/proposal_target_layer.py): a permuted copy of the whole BEV map, features for every proposal, a
+ * host loop over frames and classes with one boxes_iou3d_gpu call each, np.random draws on the host, two .item() calls in the
+ * loss.  Additive entries: the ABI version does not move.  fp32 arithmetic inside, every product and sum rounded on its own,
+ * cos / sin correctly rounded; no atomics, every float sum in a fixed order (two calls are bit for bit equal), no allocation, no host
+ * synchronisation, launch geometry a function of the shapes alone: every call can be captured in a graph.  Argument errors
+ * (LINK_ERR_ARG) are returned before anything touches a device.
+ *
+ * link_roi_bev_features: one launch.  bev = the map [batch, c, h, w] in io_dtype, read in place through strides int64[4] (host;
+ *   elements from one frame / channel / row / column to the next, each in [0, 2^40)): contiguous NCHW, channels_last and slices
+ *   alike.  boxes float[batch, r, box_len], box_len 7..64, heading in column rot_col, extents in columns 3, 4.  labels int64[batch, r]
+ *   (nullable): a row with label 0 is an unused slot.  sel int32[batch, s] (nullable; then s == r): output row j of frame b reads
+ *   box sel[b, j]; repeats allowed; an index outside [0, r) is an unused slot.  out [batch, s, num_point c] in io_dtype, the channels
+ *   of point p at [p c, (p + 1) c); an unused slot gives a row of zeros.
+ *   Points (two_stage.py:51-78): the centre; with num_point 5 also the midpoints of the front, back, left and right edges:
+ *   corners (-,-), (-,+), (+,+), (+,-) of (dx, dy) / 2 rotated by x' = x cos + y sin, y' = -x sin + y cos, plus the centre; front =
+ *   (c0 + c1) / 2, back = (c2 + c3) / 2, left = (c0 + c3) / 2, right = (c1 + c2) / 2.
+ *   Map coordinates: ((x - pc_start[0]) / voxel_size[0]) / out_stride and likewise y, IEEE divisions.
+ *   Interpolation (center_utils.py:92-121): x0 = floor(x), x1 = x0 + 1, both clamped to [0, w - 1] (y alike), the four weights from
+ *   the CLAMPED corners, ((Ia wa + Ib wb) + Ic wc) + Id wd with Ia = map[y0, x0], Ib = [y1, x0], Ic = [y0, x1], Id = [y1, x1];
+ *   rounded once into io_dtype.  A point off the map therefore does not get plain border replication.
+ *   One wave per (output row, point); lanes along the channels, four channels per lane in one load where the channel stride is 1,
+ *   c % 4 == 0, the other strides are multiples of 4 and both pointers are aligned to four elements.
+ *   LINK_ERR_ARG: a null pointer, an unknown io_dtype, num_point outside {1, 5}, batch outside 0..65535, c / h / w < 1, box_len or
+ *   rot_col out of range, s != r without sel, batch r or batch s num_point >= 2^31, a voxel size or out_stride that is not positive
+ *   and finite.  batch == 0 or s == 0: LINK_OK, nothing is launched.
+ *
+ * link_roi_assign: ProposalTargetLayer.forward + RoIHeadTemplate.assign_targets for a batch, two launches.
+ *   rois float[batch, r, code], code 7 or 9, heading in column 6; roi_labels int64[batch, r]; roi_scores float[batch, r];
+ *   gt float[batch, g, code + 1], the class last (g == 0: one row of zeros serves); trailing rows whose sum is 0 are cut, one row
+ *   always stays.  1 <= r <= LINK_ROI_MAX_ROIS, g <= LINK_ROI_MAX_GT, 1 <= m <= LINK_ROI_MAX_SAMPLES.
+ *   Overlaps: boxes_iou3d_gpu's formula (to_pcdet on both sides, the rotated BEV overlap of section I times the height overlap,
+ *   over max(vol_a + vol_b - overlap, 1e-6)) of columns 0..6 of every ROI against every ground-truth row that counts; by_class: only
+ *   rows whose class (truncated to an integer) equals the ROI's label, and an ROI without such a row keeps overlap 0 and
+ *   assignment 0.  The maximum, the lowest index among equals: max_overlaps float[batch, r], gt_assignment int32[batch, r].
+ *   code 9 needs by_class (the reference's other branch asserts 7 columns).
+ *   Sampling (subsample_rois, :133-208), one workgroup per frame: fg = overlap >= min(reg_fg, cls_fg); easy bg = overlap <
+ *   cls_bg_lo; hard bg = overlap < reg_fg and >= cls_bg_lo; each list in ascending ROI order.  fg_per_image = fg_ratio m rounded
+ *   half to even.  With fg and bg: min(fg_per_image, |fg|) foreground rows without replacement -- the candidates with the smallest
+ *   noise[b, i], in ascending order of (noise, i) -- then m minus that background rows; fg only: m draws with replacement; bg
+ *   only: m background rows.  Background: with both lists min(int(n hard_bg_ratio), |hard|) hard rows then easy rows, else all from
+ *   the list that exists.  Every draw with replacement for output slot j takes entry min(floor(noise[b, r + j] n), n - 1) of its
+ *   list of n.  noise float[batch, r + m] in [0, 1).  No candidate at all (overlaps that are not finite): status[b] =
+ *   LINK_ROI_STATUS_NO_CANDIDATE and every slot names row 0.  sel_in int32[batch, m] (nullable) replaces the sampling (noise may
+ *   then be NULL); an index outside [0, r) reads row 0 and sets LINK_ROI_STATUS_BAD_INDEX.
+ *   Targets of the m rows, written in full: sel int32, rois, roi_labels int64, roi_scores, gt_iou_of_rois (= max_overlaps),
+ *   gt_of_rois_src float[.., code + 1], reg_valid_mask int64 (overlap > reg_fg), rcnn_cls_labels float (soft_labels 0: overlap >
+ *   cls_fg, -1 where cls_bg < overlap < cls_fg; 1: 1 above cls_fg, 0 below cls_bg, (overlap - cls_bg) / (cls_fg - cls_bg) between),
+ *   gt_of_rois float[.., code + 1] in the ROI's canonical frame (roi_head_template.py:52-82): ry = limit_period(heading, 0.5, 2 pi);
+ *   columns 0..5 minus the ROI's, column 6 minus ry, columns 0, 1 rotated by -ry (x' = x cos + y sin, y' = -x sin + y cos), columns
+ *   7, 8 minus the ROI's for code 9; the heading floor-mod 2 pi, plus pi floor-mod 2 pi where it lies strictly between pi / 2 and
+ *   3 pi / 2, minus 2 pi where above pi, clamped to +-pi / 2.
+ *   LINK_ERR_ARG: a null pointer (gt with g == 0, sel_in, and noise with sel_in excepted), code outside {7, 9}, sizes out of range, a
+ *   ratio outside [0, 1], thresholds that are not finite or not ordered cls_bg_lo <= reg_fg, cls_bg_lo <= cls_fg, cls_bg < cls_fg.
+ *
+ * link_roi_loss_forward / link_roi_loss_backward: RoIHeadTemplate.get_loss with CLS_LOSS BinaryCrossEntropy and REG_LOSS L1; one
+ *   workgroup each.  rcnn_cls [n], rcnn_reg [n, code] in io_dtype, 1 <= n <= LINK_ROI_MAX_LOSS_ROWS; the targets of link_roi_assign.
+ *   cls = sum over rows with label >= 0 of -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)), p = sigmoid(x), over
+ *   max(number of such rows, 1), times cls_weight; a row with label < 0 is not read.  reg = sum over rows with reg_valid_mask > 0 and
+ *   columns of |reg - gt_of_rois| code_weights[c] over max(fg_sum, 1), times reg_weight, selected on the device.  out float[4]
+ *   (device) = total, cls, reg, fg_sum.  Forward also writes the gradients for an upstream of 1: unit_cls float[n] (autograd's
+ *   ((p - t) / max(p (1 - p), 1e-12)) p (1 - p) over the count, weighted) and unit_reg float[n, code]; backward multiplies them by
+ *   upstream[0], a DEVICE scalar, and writes both gradients in io_dtype, rounded once.  Sums: rows t, t + 256, .. per thread in
+ *   ascending order, then a tree of fixed shape.
+ *
+ * link_roi_refine: generate_predicted_boxes + TwoStageDetector.post_process, one workgroup per frame.  Per slot with label != 0:
+ *   v = rcnn_reg + the ROI with its centre zeroed; columns 0, 1 rotated by the ROI's heading (x' = x cos + y sin, y' = -x sin + y
+ *   cos), then the centre added to columns 0..2; score = sqrt(sigmoid(rcnn_cls) roi_score); label - 1; for code 9 the columns reordered
+ *   to 0..5, 7, 8, 6.  The slots in use are packed to the front of boxes float[batch, r, code], scores float[batch, r], labels
+ *   int64[batch, r] in slot order; the rest is zeros with label -1; counts int32[batch].
+ * ============================================================================================= */
+#define LINK_ROI_MAX_ROIS 4096
+#define LINK_ROI_MAX_GT 512
+#define LINK_ROI_MAX_SAMPLES 1024
+#define LINK_ROI_MAX_LOSS_ROWS (1 << 20)
+#define LINK_ROI_STATUS_NO_CANDIDATE 1
+#define LINK_ROI_STATUS_BAD_INDEX 2
+int link_roi_bev_features(const void *bev, int32_t io_dtype, const int64_t *strides /* host [4] */, int32_t batch, int32_t c, int32_t h,
+                          int32_t w, const float *boxes /* [batch, r, box_len] */, int64_t r, int32_t box_len, int32_t rot_col,
+                          const int64_t *labels /* [batch, r], nullable */, const int32_t *sel /* [batch, s], nullable */, int64_t s,
+                          int32_t num_point, const float *pc_start /* host [2] */, const float *voxel_size /* host [2] */,
+                          float out_stride, void *out /* [batch, s, num_point c] */, void *stream);
+int link_roi_assign(const float *rois, const int64_t *roi_labels, const float *roi_scores, const float *gt /* [batch, g, code + 1] */,
+                    const float *noise /* [batch, r + m] */, const int32_t *sel_in /* [batch, m], nullable */, int32_t batch, int64_t r,
+                    int64_t g, int64_t m, int32_t code, double fg_ratio, int32_t by_class, int32_t soft_labels, double cls_fg_thresh,
+                    double cls_bg_thresh, double cls_bg_thresh_lo, double hard_bg_ratio, double reg_fg_thresh,
+                    float *max_overlaps /* [batch, r] */, int32_t *gt_assignment /* [batch, r] */, int32_t *sel /* [batch, m] */,
+                    float *out_rois, int64_t *out_roi_labels, float *out_roi_scores, float *gt_iou_of_rois, float *gt_of_rois_src,
+                    float *gt_of_rois, int64_t *reg_valid_mask, float *rcnn_cls_labels, int32_t *status /* [batch] */, void *stream);
+int link_roi_loss_forward(const void *rcnn_cls, const void *rcnn_reg, int32_t io_dtype, int64_t n, int32_t code,
+                          const float *rcnn_cls_labels, const float *gt_of_rois, const int64_t *reg_valid_mask,
+                          const float *code_weights /* host [code] */, float rcnn_cls_weight, float rcnn_reg_weight, float *out /* [4] */,
+                          float *unit_cls /* [n] */, float *unit_reg /* [n, code] */, void *stream);
+int link_roi_loss_backward(const float *unit_cls, const float *unit_reg, const float *upstream /* device scalar */, int64_t n,
+                           int32_t code, int32_t io_dtype, void *grad_cls, void *grad_reg, void *stream);
+int link_roi_refine(const float *rois, const int64_t *roi_labels, const float *roi_scores, const void *rcnn_cls, const void *rcnn_reg,
+                    int32_t io_dtype, int32_t batch, int64_t r, int32_t code, float *boxes, float *scores, int64_t *labels,
+                    int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "liblink_amd.so")
@@ -134,6 +134,8 @@ SEGEVAL_ROWS, SEGEVAL_PREDICTIONS = 0, 1                      # link_seg_vote_ev
 SEGEVAL_MAX_VOTES = 16
 
 
+ROI_MAX_ROIS, ROI_MAX_GT, ROI_MAX_SAMPLES, ROI_MAX_LOSS_ROWS = 4096, 512, 1024, 1 << 20     # section O limits
+ROI_STATUS_NO_CANDIDATE, ROI_STATUS_BAD_INDEX = 1, 2
 CENTER_LOGITS, CENTER_PROBAS = 0, 1                           # link_center_loss_forward::input_kind
 CENTER_MAX_TASKS, CENTER_MAX_CLASSES, CENTER_MAX_OBJECTS, CENTER_MAX_SLOTS, CENTER_MAX_BATCH = 8, 16, 2048, 4096, 1024
 STRUCT_CENTER_ASSIGN_GEOM = 9                                 # its id for link_abi_struct_size
@@ -356,6 +358,15 @@ SIGNATURES = {
     "link_center_decode_flip4": (c_int, [c_void_p] * 6 + [c_int32] * 4 + [POINTER(LinkCenterGeom)] + [c_void_p] * 5),
     "link_nms_mask_classwise": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "link_tta_rotate_back": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
+    # section O: two-stage ROI head -- BEV features, target assignment, loss, refinement (csrc/roihead.hip)
+    "link_roi_bev_features": (c_int, [c_void_p, c_int32, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_int64, c_int32, POINTER(c_float), POINTER(c_float), c_float, c_void_p, c_void_p]),
+    "link_roi_assign": (c_int, [c_void_p] * 6 + [c_int32, c_int64, c_int64, c_int64, c_int32, c_double, c_int32, c_int32] + [c_double] * 5 +
+                        [c_void_p] * 13),
+    "link_roi_loss_forward": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_float), c_float,
+                                      c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "link_roi_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "link_roi_refine": (c_int, [c_void_p] * 5 + [c_int32, c_int32, c_int64, c_int32] + [c_void_p] * 5),
 }
 
 _lib = None
