@@ -1524,6 +1524,118 @@ int link_roi_refine(const float *rois, const int64_t *roi_labels, const float *r
                     int32_t io_dtype, int32_t batch, int64_t r, int32_t code, float *boxes, float *scores, int64_t *labels,
                     int32_t *counts, void *stream);
 
+/* =============================================================================================
+ * P. Detection training front end (csrc/detaug.hip): points against rotated boxes, BEV collisions, ground-truth paste, global augmentation
+ *
+ * What the reference's training pipeline (detection/det3d/datasets/pipelines/preprocess.py::Preprocess) does on the host between
+ * "points and annotations are loaded" and the voxeliser: box_np_ops.points_in_rbbox / points_count_rbbox (the minimum-points
+ * filter), box_np_ops.center_to_corner_box2d and core/sampler/preprocess.py::box_collision_test (the ground-truth sampler's
+ * acceptance test), the sampler's scan and paste, the four global transforms, the shuffle and the range filter on the boxes.
+ * Additive entries: the ABI version does not move.  fp32 arithmetic inside, every product and sum
+ * rounded on its own, cos / sin correctly rounded; integer atomics only, so two calls are bit for bit equal; no allocation, no host
+ * synchronisation, launch geometry a function of the shapes alone: every call can be captured in a graph.  Argument errors
+ * (LINK_ERR_ARG) are returned before anything touches a device.
+ *
+ * link_points_in_rbbox: one launch (plus the clearing of counts).  points float[n_points, ndim], ndim 3..64, x y z first.
+ *   point_offsets int32[batch + 1] (device; NULL needs batch == 1: all points belong to frame 0): frame b owns rows
+ *   [point_offsets[b], point_offsets[b + 1]), cut to [0, n_points].  boxes float[batch, n_boxes, box_len], box_len 7..64: centre,
+ *   extents, heading in the LAST column; the centre is the box's middle on all three axes (origin (0.5, 0.5, 0.5)).
+ *   A point is inside when, with q = p - centre turned back by the heading (x = qx cos - qy sin, y = qx sin + qy cos: the inverse of
+ *   rotation_3d_in_axis(axis = 2), which turns clockwise for a positive angle), |x| < dx / 2, |y| < dy / 2 and |qz| < dz / 2, all
+ *   strictly: what geometry.py:273 decides with `sign >= 0` means outside.  A box with a zero extent holds nothing; a NaN
+ *   coordinate is in no box.  mask uint8[n_points, n_boxes] (nullable), 1 = inside, row p against the boxes of p's frame; rows no
+ *   frame owns are not written.  counts int32[batch, n_boxes] (nullable): points of the frame inside each box; one wave reduction
+ *   and one integer atomic per (wave, box).  At least one of mask and counts.
+ *   LINK_ERR_ARG: sizes out of range (batch 1..65535, n_points < 2^31 - 256, n_boxes <= 2^24, n_points n_boxes <= 2^40 with a
+ *   mask), a null pointer.  n_boxes == 0: LINK_OK, nothing is launched.
+ *
+ * link_box2d_corners: box_np_ops.center_to_corner_box2d.  centers float[n, 2], dims float[n, 2], angles float[n] (nullable: no
+ *   rotation) -> out float[n, 4, 2]: the corners (-,-), (-,+), (+,+), (+,-) of dims (u - origin), turned by x' = x cos + y sin,
+ *   y' = -x sin + y cos, plus the centre: clockwise from the minimum corner, the order link_box_collision's `clockwise` names.
+ *
+ * link_box_collision: box_collision_test.  corners_a float[n, 4, 2], corners_b float[k, 4, 2] -> out uint8[n, k].  A pair collides
+ *   when the axis-aligned bounds of the two quadrilaterals overlap by more than 0 on both axes, and then either one of the 16
+ *   pairs of edges (A B of a, C D of b) crosses -- acd != bcd and abc != abd with acd = (Dy - Ay)(Cx - Ax) > (Cy - Ay)(Dx - Ax)
+ *   and likewise -- or one quadrilateral holds all four corners of the other strictly (cross >= 0 on any edge: not held).
+ *   n k < 2^31 - 256.
+ *
+ * link_detaug_sample: DataBaseSamplerV2.sample_all without group sampling (sample_ops.py:97-172, 250-296) and the bookkeeping of
+ *   Preprocess.__call__ around it (datasets/pipelines/preprocess.py:73-122), one launch, one workgroup per frame.
+ *   gt_boxes float[batch, max_gt, box_len], box_len 7 or 9, heading last; gt_classes int32[batch, max_gt]: 0 an empty slot (or a
+ *   DontCare row), k >= 1 the k-th name of the detector's class list, negative a name outside that list (it stays in the avoid set
+ *   and is dropped from the output, as gt_boxes_mask does); gt_counts int32[batch, max_gt] (link_points_in_rbbox's counts on the
+ *   untransformed scene; NULL with min_points <= 0): a row with fewer than min_points points does not survive.
+ *   The database: db_boxes float[db_size, box_len], db_classes int32[db_size] (>= 1), db_offsets int64[db_size + 1] (rows of the
+ *   packed object-centred points).  candidates int32[batch, n_groups, max_candidates] with cand_len int32[batch, n_groups]:
+ *   database indices in the order the reference's BatchSampler would hand them out.
+ *   For group q in order: n = clamp(round_half_even(rate (group_max[q] - survivors of class group_class[q])), 0, cand_len) heads of
+ *   the list are tested with link_box_collision's rule against the avoid set (the surviving ground truth, then everything
+ *   accepted for earlier groups) and against each other; candidate i is rejected when it collides with the avoid set, with an
+ *   accepted earlier candidate or with ANY later candidate of the n (sample_class_v2 clears a rejected row and column only when
+ *   it reaches it); the accepted join the avoid set.  An index outside [0, db_size) is rejected and sets
+ *   LINK_DETAUG_STATUS_BAD_INDEX.
+ *   Out, with max_accept = n_groups max_candidates: accepted int32[batch, max_accept] (database indices in acceptance order, then
+ *   -1), paste_start int32[batch, max_accept + 1] (first point slot of every accepted object, the pasted total from n_accept on),
+ *   n_accept int32[batch]; merged_boxes float[batch, max_gt + max_accept, box_len] / merged_classes int32[..] / n_merged
+ *   int32[batch]: the survivors of a class >= 1 in order, then the accepted database boxes; status int32[batch], written in full.
+ *   LINK_ERR_ARG: n_groups > LINK_DETAUG_MAX_GROUPS, max_candidates > LINK_DETAUG_MAX_CANDIDATES, max_gt + n_groups max_candidates
+ *   > LINK_DETAUG_MAX_BOXES (the avoid set and the collision rows live in LDS), a class < 1, a negative rate, a null pointer.
+ *
+ * link_detaug_transform: the paste, random_flip_both, global_rotation, global_scaling_v2, global_translate_ (core/sampler/
+ *   preprocess.py:803-839, 771-788, 940-962), the point shuffle and filter_gt_box_outside_range (:108-122); two launches.
+ *   draws float[batch, 7], device: u_flip_x, u_flip_y, u_rot, u_scale uniform in [0, 1) and three standard normals.  A flip happens
+ *   when its u >= 1 - flip_probability (np.random.choice's rule); angle = rot_lo + (rot_hi - rot_lo) u_rot and scale likewise, in
+ *   double; the translation is std[0] n0, std[1] n1, std[0] n2 (the reference draws z with std[0]), added in double.
+ *   Points: slot r of frame b is, in this order, a point of the accepted objects (object-centred point + its box centre, in
+ *   acceptance order), a point of the frame's scene (points float[n_points, ndim] by point_offsets int32[batch + 1]), or nothing;
+ *   it is transformed (x flip: y = -y; y flip: x = -x; x' = x cos + y sin, y' = -x sin + y cos; times scale; plus translation)
+ *   and written to row perm[b, r] of out_points float[batch, point_capacity, ndim]; a slot past the frame's total writes a row of
+ *   NaN (link_voxelize's range test rejects it), a frame with more points than point_capacity loses the last and sets
+ *   LINK_DETAUG_STATUS_POINTS_CUT.  perm int32[batch, point_capacity]: a permutation of 0 .. point_capacity - 1 per frame (the
+ *   reference's np.random.shuffle); an entry out of range writes nothing.
+ *   Boxes: the merged boxes get the same steps with the reference's quirks -- heading = -heading + pi (x flip), -heading + 2 pi
+ *   (y flip), + angle; the velocity columns 6, 7 of box_len 9 are flipped, rotated (in double) and scaled like every column but the
+ *   heading -- and stay when one BEV corner lies strictly inside range = xmin, ymin, xmax, ymax; the kept are packed in order into
+ *   out_boxes float[batch, max_objs, box_len] and out_classes int32[batch, max_objs] (0 = empty; rows past the count are zeros;
+ *   more than max_objs: the last are cut and LINK_DETAUG_STATUS_BOXES_CUT is set); n_boxes, n_out_points int32[batch].
+ *   status is OR-ed into what link_detaug_sample wrote.
+ * ============================================================================================= */
+#define LINK_DETAUG_MAX_GROUPS 16
+#define LINK_DETAUG_MAX_CANDIDATES 64
+#define LINK_DETAUG_MAX_BOXES 1024
+#define LINK_DETAUG_STATUS_BAD_INDEX 1
+#define LINK_DETAUG_STATUS_POINTS_CUT 2
+#define LINK_DETAUG_STATUS_BOXES_CUT 4
+typedef struct {
+  double rate;
+  int32_t n_groups, max_candidates, max_gt, min_points, box_len, reserved;
+  int32_t group_class[LINK_DETAUG_MAX_GROUPS]; /* 1-based class of every sampled group, in sample_groups' order */
+  int32_t group_max[LINK_DETAUG_MAX_GROUPS];   /* its target number of objects per frame */
+} link_detaug_sample_cfg_t;
+typedef struct {
+  double rot_lo, rot_hi, scale_lo, scale_hi, translate_std[3], flip_probability;
+  double range[4]; /* xmin, ymin, xmax, ymax */
+  int32_t max_objs, point_capacity;
+} link_detaug_transform_cfg_t;
+int link_points_in_rbbox(const float *points, int32_t ndim, const int32_t *point_offsets /* [batch + 1], device, nullable */,
+                         int32_t batch, int64_t n_points, const float *boxes /* [batch, n_boxes, box_len] */, int64_t n_boxes,
+                         int32_t box_len, uint8_t *mask /* [n_points, n_boxes], nullable */, int32_t *counts /* [batch, n_boxes], nullable */,
+                         void *stream);
+int link_box2d_corners(const float *centers, const float *dims, const float *angles /* nullable */, int64_t n, float origin,
+                       float *out /* [n, 4, 2] */, void *stream);
+int link_box_collision(const float *corners_a, int64_t n, const float *corners_b, int64_t k, int32_t clockwise,
+                       uint8_t *out /* [n, k] */, void *stream);
+int link_detaug_sample(const link_detaug_sample_cfg_t *cfg /* host */, int32_t batch, const float *gt_boxes, const int32_t *gt_classes,
+                       const int32_t *gt_counts /* nullable */, const int32_t *candidates, const int32_t *cand_len, const float *db_boxes,
+                       const int32_t *db_classes, const int64_t *db_offsets, int64_t db_size, int32_t *accepted, int32_t *paste_start,
+                       int32_t *n_accept, float *merged_boxes, int32_t *merged_classes, int32_t *n_merged, int32_t *status, void *stream);
+int link_detaug_transform(const link_detaug_transform_cfg_t *cfg /* host */, int32_t batch, const float *draws, const float *points,
+                          const int32_t *point_offsets, int64_t n_points, int32_t ndim, const float *db_points, const int64_t *db_offsets,
+                          const float *db_boxes, int32_t box_len, const int32_t *accepted, const int32_t *paste_start,
+                          const int32_t *n_accept, int32_t max_accept, const int32_t *perm, float *out_points, const float *merged_boxes,
+                          const int32_t *merged_classes, const int32_t *n_merged, int32_t max_merged, float *out_boxes,
+                          int32_t *out_classes, int32_t *n_boxes, int32_t *n_out_points, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

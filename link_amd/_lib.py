@@ -148,6 +148,24 @@ class LinkCenterAssignGeom(Structure):
                 ("num_classes", c_int32 * 8)]
 
 
+DETAUG_MAX_GROUPS, DETAUG_MAX_CANDIDATES, DETAUG_MAX_BOXES = 16, 64, 1024     # section P limits
+DETAUG_STATUS_BAD_INDEX, DETAUG_STATUS_POINTS_CUT, DETAUG_STATUS_BOXES_CUT = 1, 2, 4
+STRUCT_DETAUG_SAMPLE_CFG, STRUCT_DETAUG_TRANSFORM_CFG = 11, 12       # their ids for link_abi_struct_size (10 is kept unassigned)
+
+
+class LinkDetaugSampleCfg(Structure):
+    """link_detaug_sample_cfg_t (section P: the ground-truth sampler's scan)"""
+    _fields_ = [("rate", c_double)] + [(k, c_int32) for k in ("n_groups", "max_candidates", "max_gt", "min_points", "box_len", "reserved")] + \
+               [("group_class", c_int32 * 16), ("group_max", c_int32 * 16)]
+
+
+class LinkDetaugTransformCfg(Structure):
+    """link_detaug_transform_cfg_t (section P: paste, global transforms, range filter)"""
+    _fields_ = [(k, c_double) for k in ("rot_lo", "rot_hi", "scale_lo", "scale_hi")] + \
+               [("translate_std", c_double * 3), ("flip_probability", c_double), ("range", c_double * 4), ("max_objs", c_int32),
+                ("point_capacity", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -367,6 +385,14 @@ SIGNATURES = {
                                       c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "link_roi_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "link_roi_refine": (c_int, [c_void_p] * 5 + [c_int32, c_int32, c_int64, c_int32] + [c_void_p] * 5),
+    # section P: geometry of the detection training front end -- points in rotated boxes, BEV corners, collisions (csrc/detaug.hip)
+    "link_points_in_rbbox": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "link_box2d_corners": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
+    "link_box_collision": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "link_detaug_sample": (c_int, [POINTER(LinkDetaugSampleCfg), c_int32] + [c_void_p] * 8 + [c_int64] + [c_void_p] * 8),
+    "link_detaug_transform": (c_int, [POINTER(LinkDetaugTransformCfg), c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                      c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
 }
 
 _lib = None
@@ -391,8 +417,10 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
         if handle.link_abi_version() != ABI_VERSION:
             raise LinkAmdError("liblink_amd.so ABI version mismatch; rebuild with link_amd/build.py")
-        for which, cls in enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
-                                      LinkVoxelizeGeom, LinkCenterAssignGeom)):
+        structs = list(enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
+                                  LinkVoxelizeGeom, LinkCenterAssignGeom)))
+        structs += [(STRUCT_DETAUG_SAMPLE_CFG, LinkDetaugSampleCfg), (STRUCT_DETAUG_TRANSFORM_CFG, LinkDetaugTransformCfg)]
+        for which, cls in structs:
             if handle.link_abi_struct_size(which) != ctypes.sizeof(cls):
                 raise LinkAmdError(f"liblink_amd.so: layout of {cls.__name__} differs from include/link_amd.h "
                                    f"({ctypes.sizeof(cls)} bytes here, {handle.link_abi_struct_size(which)} in the library)")

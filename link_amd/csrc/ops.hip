@@ -31,6 +31,9 @@ extern "C" int32_t link_abi_struct_size(int32_t which) {
     case 7: return (int32_t)sizeof(link_block_args_t);
     case 8: return (int32_t)sizeof(link_voxelize_geom_t);
     case 9: return (int32_t)sizeof(link_center_assign_geom_t);
+    // 10 stays unassigned: the checks of sections N and O use it as "no such struct"
+    case 11: return (int32_t)sizeof(link_detaug_sample_cfg_t);
+    case 12: return (int32_t)sizeof(link_detaug_transform_cfg_t);
     default: return -1;
   }
 }
