@@ -1636,6 +1636,66 @@ int link_detaug_transform(const link_detaug_transform_cfg_t *cfg /* host */, int
                           const int32_t *merged_classes, const int32_t *n_merged, int32_t max_merged, float *out_boxes,
                           int32_t *out_classes, int32_t *n_boxes, int32_t *n_out_points, int32_t *status, void *stream);
 
+/* =============================================================================================
+ * Q. Multi-object tracker (csrc/track.hip): greedy centre matching of one frame against the track list, for a batch of sequences
+ *
+ * The CenterPoint tracker of detection/tools/nusc_tracking/pub_tracker.py:45-154 (with track_utils.py:3-12) and
+ * detection/tools/waymo_tracking/tracker.py:42-136.  Additive entries: the ABI version does not move.  One launch, one workgroup
+ * per sequence, no allocation, no host synchronisation, ordinary vector stores only: a call can be captured in a graph.
+ * Argument errors (LINK_ERR_ARG) are returned before anything touches a device.
+ *
+ * link_track_state_bytes(capacity): bytes of ONE sequence's state, 0 for a capacity outside 1..LINK_TRACK_MAX_CAPACITY.  The
+ *   caller owns state[n_seq][that many bytes], zeroed before the first call (all zero = no tracks, id_count 0).  Layout of one
+ *   sequence: int32 header[8] = n_tracks, id_count, status, capacity, 4 x reserved; then the track list, then a second list of
+ *   the same shape which a call builds the new list in before it replaces the first (what a caller reads is always the first).
+ *   One list of K = capacity tracks: ct double[K][2], tracking double[K][2], label int32[K] (tracking label), tracking_id
+ *   int32[K], age int32[K], active int32[K], src int32[K] (the detection slot, -1 for a track carried over without one).
+ *
+ * link_track_step: advances n_seq independent sequences by one frame.  boxes float[n_seq, n, box_len], box_len 6..64: centre in
+ *   columns 0..2, velocity in columns box_len - 3 and box_len - 2 (6 and 7 of a 9-wide box); scores float[n_seq, n]; labels
+ *   int32 or int64 [n_seq, n] (labels_int64), -1 (or anything outside the label table) an unused slot; counts int32[n_seq]
+ *   (nullable: only the labels mark unused slots); time_lag double[n_seq]; reset uint8[n_seq] (nullable); pose double[n_seq, 12]
+ *   (nullable): the row-major 3 x 4 lidar-to-global transform.  All on the device.
+ *   The steps, in this arithmetic:
+ *    1. reset[s] clears the list and id_count before the frame (PubTracker.reset).
+ *    2. A frame with no detection of a tracked class -- none at all, or only untracked ones -- clears the list, returns nothing
+ *       and keeps id_count (pub_tracker.py:50-52; for untracked-only frames the reference raises an IndexError at :71 -- a
+ *       deliberate difference).
+ *    3. Detections whose label maps to -1 are removed; the order of the rest is kept (:55-63).
+ *    4. With a pose, in double: ct = ((r0 x + r1 y) + r2 z) + t per row, velocity = (r0 vx + r1 vy) per row; without, the doubles
+ *       of the floats.
+ *    5. tracking = velocity * -1 * time_lag in double (:61).
+ *    6. The matched position is float(ct + double(float(tracking))) (:71-74); 7. a track's centre is float(ct) (:84-85).
+ *    8. dist = sqrt(dx dx + dy dy) in float, every operation rounded on its own, the root correctly rounded (:88-90).
+ *    9. A pair is invalid when dist > max_dist[label of the detection] (strictly) or the labels differ (:92-93).
+ *   10. Greedy scan in detection order; a detection takes the first minimum among the valid free tracks (track_utils.py:7-11).
+ *   11. The new list: matched detections in detection order (the track's id, age 1, active + 1; :123-128), unmatched detections
+ *       in detection order (id = ++id_count, age 1, active 1; with a score threshold only those with score > threshold,
+ *       tracker.py:113), unmatched old tracks with age < max_age in their old order (age + 1, active 0, ct -= tracking: the move
+ *       forward ignores the present time lag; tracking unchanged; :140-151).  12. A carried-over track that matches later gets
+ *       active 1.
+ *   Out: det_tracking_id int32[n_seq, n] (-1: filtered, dropped or unused), det_active int32[n_seq, n] (0 there), and the state.
+ *   status bit 0 (LINK_TRACK_STATUS_OVERFLOW, rewritten by every call): the new list had more than capacity entries; its tail
+ *   was dropped, which is carried-over tracks only since n <= capacity.  Non-finite centres or velocities: unspecified matches.
+ *   LINK_ERR_ARG: a null pointer, n > capacity, capacity or a table size out of range, a label_map entry outside
+ *   -1 .. n_track_labels - 1, a max_dist that is negative, NaN or >= 1e16 (the reference's "no match" sentinel), max_age < 0.
+ * ============================================================================================= */
+#define LINK_TRACK_MAX_LABELS 32
+#define LINK_TRACK_MAX_CAPACITY 1024
+#define LINK_TRACK_STATUS_OVERFLOW 1
+typedef struct {
+  int32_t n_det_labels, n_track_labels, max_age, capacity;
+  float score_thresh; /* NaN: no threshold (the nuScenes form) */
+  int32_t reserved;
+  int32_t label_map[LINK_TRACK_MAX_LABELS]; /* detection label -> tracking label, -1 = not tracked */
+  float max_dist[LINK_TRACK_MAX_LABELS];    /* per tracking label */
+} link_track_cfg_t;
+size_t link_track_state_bytes(int32_t capacity);
+int link_track_step(const link_track_cfg_t *cfg /* host */, int32_t n_seq, int32_t n, int32_t box_len, const float *boxes,
+                    const float *scores, const void *labels, int32_t labels_int64, const int32_t *counts /* nullable */,
+                    const double *time_lag, const uint8_t *reset /* nullable */, const double *pose /* nullable */, void *state,
+                    int32_t *det_tracking_id, int32_t *det_active, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

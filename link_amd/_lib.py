@@ -166,6 +166,17 @@ class LinkDetaugTransformCfg(Structure):
                 ("point_capacity", c_int32)]
 
 
+TRACK_MAX_LABELS, TRACK_MAX_CAPACITY, TRACK_STATUS_OVERFLOW = 32, 1024, 1      # section Q limits
+TRACK_HDR_BYTES = 32                                          # int32 n_tracks, id_count, status, capacity, 4 x reserved
+STRUCT_TRACK_CFG = 13                                         # its id for link_abi_struct_size
+
+
+class LinkTrackCfg(Structure):
+    """link_track_cfg_t (section Q: the tracker's settings)"""
+    _fields_ = [(k, c_int32) for k in ("n_det_labels", "n_track_labels", "max_age", "capacity")] + \
+               [("score_thresh", c_float), ("reserved", c_int32), ("label_map", c_int32 * 32), ("max_dist", c_float * 32)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -393,6 +404,9 @@ SIGNATURES = {
     "link_detaug_transform": (c_int, [POINTER(LinkDetaugTransformCfg), c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                       c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
+    # section Q: multi-object tracker -- greedy centre matching for a batch of sequences (csrc/track.hip)
+    "link_track_state_bytes": (c_size_t, [c_int32]),
+    "link_track_step": (c_int, [POINTER(LinkTrackCfg), c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32] + [c_void_p] * 8),
 }
 
 _lib = None
@@ -419,7 +433,8 @@ def lib() -> ctypes.CDLL:
             raise LinkAmdError("liblink_amd.so ABI version mismatch; rebuild with link_amd/build.py")
         structs = list(enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
                                   LinkVoxelizeGeom, LinkCenterAssignGeom)))
-        structs += [(STRUCT_DETAUG_SAMPLE_CFG, LinkDetaugSampleCfg), (STRUCT_DETAUG_TRANSFORM_CFG, LinkDetaugTransformCfg)]
+        structs += [(STRUCT_DETAUG_SAMPLE_CFG, LinkDetaugSampleCfg), (STRUCT_DETAUG_TRANSFORM_CFG, LinkDetaugTransformCfg),
+                    (STRUCT_TRACK_CFG, LinkTrackCfg)]
         for which, cls in structs:
             if handle.link_abi_struct_size(which) != ctypes.sizeof(cls):
                 raise LinkAmdError(f"liblink_amd.so: layout of {cls.__name__} differs from include/link_amd.h "
