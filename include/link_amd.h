@@ -1696,6 +1696,67 @@ int link_track_step(const link_track_cfg_t *cfg /* host */, int32_t n_seq, int32
                     const double *time_lag, const uint8_t *reset /* nullable */, const double *pose /* nullable */, void *state,
                     int32_t *det_tracking_id, int32_t *det_active, void *stream);
 
+/* =============================================================================================
+ * R. Deformable convolution, DCN v1 (csrc/dcn.hip): forward, grad_input + grad_offset, grad_weight
+ *
+ * The DeformConv of detection/det3d/ops/dcn (deform_conv.py:14-112 over src/deform_conv_cuda.cpp and
+ * src/deform_conv_cuda_kernel.cu), which CenterHead(dcn_head=True) builds its FeatureAdaption modules on
+ * (models/bbox_heads/center_head.py:27-65).  Additive entries: the ABI version does not move.  Modulated (v2) convolution and
+ * deformable ROI pooling are not built.
+ *
+ * input [B, C, H, W], offset [B, dg 2 kh kw, Ho, Wo] (channel 2 (i kw + j) of deformable group g is the row offset of tap (i, j),
+ * the next one its column offset), weight [O, C, kh, kw], output [B, O, Ho, Wo], all contiguous, no bias;
+ * Ho = (H + 2 pad_h - (dil_h (kh - 1) + 1)) / stride_h + 1, Wo likewise.  For output pixel (ho, wo), tap (i, j) and input channel c
+ * of deformable group g = c / (C / dg): h = ho stride_h - pad_h + i dil_h + dh, w = wo stride_w - pad_w + j dil_w + dw; the sample
+ * is the bilinear value at (h, w) with floor for the low corner, a corner off the map counting 0, and a sample that fails
+ * h > -1 && w > -1 && h < H && w < W counting 0 (deformable_im2col_gpu_kernel, deform_conv_cuda_kernel.cu:191).  The output is
+ * the sum over c, i, j of weight[o, c, i, j] sample.  A deliberate difference: the range test is made on the float value before any
+ * conversion to an index, so a NaN, an infinity or an offset no int holds contributes exactly 0, receives a zero offset gradient
+ * and scatters nothing (the reference's backward converts such a value to int, which is undefined).
+ *
+ * No column matrix is written to memory: the columns are sampled into LDS and multiplied on the matrix cores with the exact
+ * f32-input instruction, accumulating in fp32.  LINK_DCN_RELU applies max(x, 0) to the output and, in the two backward entries,
+ * masks grad_out where output <= 0 (they then read `output`, which may be null otherwise).  io_dtype: the forward entry takes
+ * LINK_IO_F32 / LINK_IO_F16 / LINK_IO_BF16 tensors (all four in that type, widened on load, rounded to nearest even on store;
+ * coordinates, samples and sums are fp32); the backward entries are fp32 only (LINK_ERR_ARG otherwise; the Python layer widens).
+ *
+ * Every entry launches on the caller's stream, allocates nothing, reads nothing back and keeps no state: a call can be captured
+ * in a graph.  grad_offset and grad_weight are reproducible run to run (fixed summation order; grad_weight goes through
+ * per-wave partials in the workspace and one fixed-order reduce).  grad_input is zeroed by the call (hipMemsetAsync on the stream)
+ * and summed with no-return fp32 atomics, so its last bits depend on the order in which the adds arrive.
+ *
+ * Envelope: groups == 1, kh kw <= LINK_DCN_MAX_TAPS, C and O <= LINK_DCN_MAX_CHANNELS, deformable_groups dividing C (any channel
+ * count per group: chunks are padded inside LDS), stride and dilation >= 1, padding >= 0, Ho and Wo >= 1, every tensor at most
+ * 2^31 elements, offset_channels == dg 2 kh kw.  Outside it, or with a null pointer: LINK_ERR_ARG before anything touches a device
+ * (link_deform_conv_workspace_bytes: 0).  grad_input or grad_offset may be null (not both): that gradient is not computed.
+ * LINK_ERR_WORKSPACE for fewer workspace bytes than the size helper names.
+ *
+ * link_deform_conv_forward          replaces deform_conv_forward_cuda (deform_conv_cuda.cpp:152)
+ * link_deform_conv_backward_data    replaces deform_conv_backward_input_cuda (:262; deformable_col2im_gpu_kernel and
+ *                                   deformable_col2im_coord_gpu_kernel with get_coordinate_weight, deform_conv_cuda_kernel.cu:280, 374, 146)
+ * link_deform_conv_backward_weight  replaces deform_conv_backward_parameters_cuda (:376)
+ * ============================================================================================= */
+#define LINK_DCN_MAX_TAPS 49
+#define LINK_DCN_MAX_CHANNELS 256
+#define LINK_DCN_RELU 1
+typedef struct {
+  int32_t batch, c, h, w, o, kh, kw;
+  int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+  int32_t groups, deformable_groups, offset_channels;
+  int32_t io_dtype; /* LINK_IO_* */
+  int32_t flags;    /* LINK_DCN_RELU */
+} link_deform_conv_geom_t;            /* link_abi_struct_size(14) */
+size_t link_deform_conv_workspace_bytes(const link_deform_conv_geom_t *geom);
+int link_deform_conv_forward(const link_deform_conv_geom_t *geom, const void *input, const void *offset, const void *weight,
+                             void *output, void *stream);
+int link_deform_conv_backward_data(const link_deform_conv_geom_t *geom, const float *input, const float *offset,
+                                   const float *weight, const float *output /* nullable without LINK_DCN_RELU */,
+                                   const float *grad_out, float *grad_input /* nullable */, float *grad_offset /* nullable */,
+                                   void *stream);
+int link_deform_conv_backward_weight(const link_deform_conv_geom_t *geom, const float *input, const float *offset,
+                                     const float *output /* nullable without LINK_DCN_RELU */, const float *grad_out,
+                                     float *grad_weight, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

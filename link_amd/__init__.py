@@ -11,10 +11,12 @@ from .aggregate import (aux_to_voxel, large_to_small, link_index_of, small_to_la
                         voxel_to_aux)
 from .elk import (Conv3d, ELKBlock, ElkCoreBatch, ElkCorePlan, SparseConvTensor, TSELKBlock, elk_core_autograd, elk_core_fused,
                   invalidate_derived_weights, spconv2ts, ts2spconv)
-from . import boxnms, centerloss, detaug, dethead, dettta, roihead, segio, segloss, tracker, voxelize
+from . import boxnms, centerloss, dcn, detaug, dethead, dettta, roihead, segio, segloss, tracker, voxelize
 from .boxnms import (boxes_iou3d_gpu, boxes_iou_bev, boxes_overlap_bev, circle_nms, install_as_iou3d_nms, nms_gpu, nms_normal_gpu,
                      nms_padded, rotate_nms_pcdet, to_pcdet)
 from .centerloss import CenterHeadLoss, CenterTargetAssigner, FastFocalLoss, RegLoss
+from .dcn import (DCNSepHead, DeformConv, DeformConvPack, FeatureAdaption, SepHead, deform_conv, deform_conv_native, deform_conv_relu,
+                  deform_conv_torch)
 from .detaug import (DatabaseSampler, DetTrainAugmenter, GTDatabase, box_collision_test, center_to_corner_box2d, install_as_box_np_ops,
                      points_count_rbbox, points_in_rbbox)
 from .dethead import CenterHeadDecoder

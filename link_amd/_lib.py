@@ -177,6 +177,16 @@ class LinkTrackCfg(Structure):
                [("score_thresh", c_float), ("reserved", c_int32), ("label_map", c_int32 * 32), ("max_dist", c_float * 32)]
 
 
+DCN_MAX_TAPS, DCN_MAX_CHANNELS, DCN_RELU = 49, 256, 1         # section R limits and flag
+STRUCT_DEFORM_CONV_GEOM = 14                                  # its id for link_abi_struct_size
+
+
+class LinkDeformConvGeom(Structure):
+    """link_deform_conv_geom_t (section R: deformable convolution)"""
+    _fields_ = [(k, c_int32) for k in ("batch", "c", "h", "w", "o", "kh", "kw", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w",
+                                       "groups", "deformable_groups", "offset_channels", "io_dtype", "flags")]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -407,6 +417,11 @@ SIGNATURES = {
     # section Q: multi-object tracker -- greedy centre matching for a batch of sequences (csrc/track.hip)
     "link_track_state_bytes": (c_size_t, [c_int32]),
     "link_track_step": (c_int, [POINTER(LinkTrackCfg), c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32] + [c_void_p] * 8),
+    # section R: deformable convolution, DCN v1 (csrc/dcn.hip)
+    "link_deform_conv_workspace_bytes": (c_size_t, [POINTER(LinkDeformConvGeom)]),
+    "link_deform_conv_forward": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 5),
+    "link_deform_conv_backward_data": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 8),
+    "link_deform_conv_backward_weight": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 6 + [c_size_t, c_void_p]),
 }
 
 _lib = None
@@ -434,7 +449,7 @@ def lib() -> ctypes.CDLL:
         structs = list(enumerate((LinkGrid, LinkElkDesc, LinkElkBuffers, LinkDcGrid, LinkDcTuning, LinkDcBuffers, LinkLeanBuffers, LinkBlockArgs,
                                   LinkVoxelizeGeom, LinkCenterAssignGeom)))
         structs += [(STRUCT_DETAUG_SAMPLE_CFG, LinkDetaugSampleCfg), (STRUCT_DETAUG_TRANSFORM_CFG, LinkDetaugTransformCfg),
-                    (STRUCT_TRACK_CFG, LinkTrackCfg)]
+                    (STRUCT_TRACK_CFG, LinkTrackCfg), (STRUCT_DEFORM_CONV_GEOM, LinkDeformConvGeom)]
         for which, cls in structs:
             if handle.link_abi_struct_size(which) != ctypes.sizeof(cls):
                 raise LinkAmdError(f"liblink_amd.so: layout of {cls.__name__} differs from include/link_amd.h "

@@ -35,6 +35,7 @@ extern "C" int32_t link_abi_struct_size(int32_t which) {
     case 11: return (int32_t)sizeof(link_detaug_sample_cfg_t);
     case 12: return (int32_t)sizeof(link_detaug_transform_cfg_t);
     case 13: return (int32_t)sizeof(link_track_cfg_t);
+    case 14: return (int32_t)sizeof(link_deform_conv_geom_t);
     default: return -1;
   }
 }
