@@ -478,6 +478,26 @@ def check(rc: int, what: str) -> None:
         raise LinkAmdError(f"{what}: {msg}" + (f" ({detail.decode()})" if detail else ""))
 
 
+def ptr(t):
+    """the data pointer of an optional tensor: None stays None (NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def point_offsets(cache: dict, device, sizes):
+    """int32 [B + 1] on the device, the running sum of `sizes`; kept in the caller's `cache` per tuple of sizes, so a call with sizes
+    seen before copies nothing from the host (a captured graph has fixed sizes: the call that warms it up leaves the tensor here).
+    A cache that holds 64 entries is emptied first."""
+    import numpy as np
+    import torch
+    key = (device, tuple(sizes))
+    t = cache.get(key)
+    if t is None:
+        if len(cache) >= 64:
+            cache.clear()
+        t = cache[key] = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).to(device)
+    return t
+
+
 def grid_from_bounds(lo, hi, s: int) -> LinkGrid:
     """Host helper (no GPU needed): block grid covering voxel coords lo..hi (inclusive)."""
     g = LinkGrid()

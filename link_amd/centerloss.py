@@ -175,15 +175,11 @@ class _Workspace:
 _WS = _Workspace()
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _reg_views(regs):
     """five data pointers (vel may be missing) and their batch strides: contiguous maps, or channel slices of one tensor"""
     ptrs, strides = [], (ctypes.c_int64 * 5)()
     for i, r in enumerate(regs):
-        ptrs.append(_ptr(r))
+        ptrs.append(L.ptr(r))
         strides[i] = 0 if r is None else (r.stride(0) if r.shape[0] > 1 else r.shape[1] * r.shape[2] * r.shape[3])   # a size-1 dimension's stride means nothing
     return ptrs, strides
 
@@ -217,10 +213,10 @@ class _CenterLossFn(torch.autograd.Function):
         cw = (ctypes.c_float * 10)(*([float(v) for v in code_weights] + [0.0] * (10 - len(code_weights))))
         ptrs, strides = _reg_views(regs)
         with torch.cuda.device(dev):
-            L.check(L.lib().link_center_loss_forward(_ptr(hm), *ptrs, strides if has_reg else None, _IO[ref.dtype], kind, _ptr(hm_target),
-                                                     _ptr(anno_box), ind.data_ptr(), mask.data_ptr(), _ptr(cat), B, K, H, W, M, cw,
-                                                     float(weight), buf.data_ptr(), buf.numel(), out.data_ptr(), _ptr(unit_hm),
-                                                     _ptr(unit_box), L.current_stream_handle()), "link_center_loss_forward")
+            L.check(L.lib().link_center_loss_forward(L.ptr(hm), *ptrs, strides if has_reg else None, _IO[ref.dtype], kind, L.ptr(hm_target),
+                                                     L.ptr(anno_box), ind.data_ptr(), mask.data_ptr(), L.ptr(cat), B, K, H, W, M, cw,
+                                                     float(weight), buf.data_ptr(), buf.numel(), out.data_ptr(), L.ptr(unit_hm),
+                                                     L.ptr(unit_box), L.current_stream_handle()), "link_center_loss_forward")
         ctx.save_for_backward(*[t for t in (unit_hm, unit_box, ind, mask) if t is not None])
         ctx.has = (hm is not None, has_reg, vel is not None)
         ctx.shape = (B, K, H, W, M)
@@ -244,8 +240,8 @@ class _CenterLossFn(torch.autograd.Function):
         if has_reg:
             grads = [torch.empty((B, _REG_CH[n], H, W), dtype=ctx.io, device=dev) if (n != "vel" or has_vel) else None for n in _REG_NAMES]
         with torch.cuda.device(dev):
-            L.check(L.lib().link_center_loss_backward(_ptr(unit_hm), _ptr(unit_box), ind.data_ptr(), mask.data_ptr(), up.data_ptr(), B, K, H, W,
-                                                      M, _IO[ctx.io], _ptr(g_hm), *[_ptr(g) for g in grads], None,
+            L.check(L.lib().link_center_loss_backward(L.ptr(unit_hm), L.ptr(unit_box), ind.data_ptr(), mask.data_ptr(), up.data_ptr(), B, K, H, W,
+                                                      M, _IO[ctx.io], L.ptr(g_hm), *[L.ptr(g) for g in grads], None,
                                                       L.current_stream_handle()), "link_center_loss_backward")
         return (g_hm, *grads, None, None, None, None, None, None, None, None)
 

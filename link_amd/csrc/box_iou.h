@@ -1,6 +1,6 @@
 // link_amd/csrc/box_iou.h -- the rotated BEV overlap of a box pair as device functions, shared by csrc/boxnms.hip (sections I) and
 // csrc/dettta.hip (section N).  Semantics: detection/det3d/ops/iou3d_nms/src/iou3d_nms_kernel.cu:35-234; the implementation notes
-// are at the head of boxnms.hip.
+// are at the head of boxnms.hip.  At its end: the geometry record and the count body the two CenterHead decoders share.
 //
 // The reference rounds every product and sum on its own and its strict inequalities decide which points exist, so contraction is
 // off for every translation unit that includes this file (from here to its end).
@@ -151,6 +151,25 @@ __device__ __forceinline__ int device_count(const int32_t *n_dev, int cap) {
   if (!n_dev) return cap;
   const int n = *n_dev;
   return n < 0 ? 0 : (n > cap ? cap : n);
+}
+
+// ---- what the two CenterHead decoders (k_center_decode, k_center_decode_flip4) share ----
+struct decode_geom {
+  float osf, vx, vy, px, py, thr, lo[3], hi[3];
+};
+
+// unmasked cells per frame, the body of the kernel behind either decoder: one workgroup of 256 threads per frame, integer sums
+// through LDS (no atomics)
+__device__ __forceinline__ void center_count_frame(const float *scores, int hw, int32_t *counts) {
+  __shared__ int part[4];
+  const float *s = scores + (int64_t)blockIdx.x * hw;
+  int c = 0;
+  for (int i = threadIdx.x; i < hw; i += 256) c += s[i] > -INFINITY ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
 }  // namespace link

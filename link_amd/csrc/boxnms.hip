@@ -167,10 +167,6 @@ __global__ __launch_bounds__(256) void k_nms_reduce(const unsigned long long *__
   if (tid == 0) *count = cnt;
 }
 
-struct decode_geom {
-  float osf, vx, vy, px, py, thr, lo[3], hi[3];
-};
-
 // center_head.py:344-421 + the masks of :461-467, one lane per cell of one frame's H x W map (NCHW maps read in place: a wave reads
 // 64 consecutive cells of every channel)
 template <bool VEL>
@@ -204,17 +200,9 @@ __global__ __launch_bounds__(256) void k_center_decode(const float *__restrict__
   scores[f + cell] = ok ? best : -INFINITY;
 }
 
-// unmasked cells per frame: one workgroup per frame, integer sums through LDS (no atomics)
+// unmasked cells per frame (box_iou.h)
 __global__ __launch_bounds__(256) void k_center_count(const float *__restrict__ scores, int hw, int32_t *__restrict__ counts) {
-  __shared__ int part[4];
-  const float *s = scores + (int64_t)blockIdx.x * hw;
-  int c = 0;
-  for (int i = threadIdx.x; i < hw; i += 256) c += s[i] > -INFINITY ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  center_count_frame(scores, hw, counts);
 }
 
 constexpr int64_t MAX_BOXES = 65535LL * PAIR_ROWS;       // grid.y of the pair kernel; 65535 * 64 boxes for the mask is above it

@@ -20,7 +20,8 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
+#include "dispatch.h"
 #include "row_io.h"
 
 #pragma clang fp contract(off)
@@ -65,57 +66,6 @@ __device__ __forceinline__ void column_of(int c, bool has_vel, int &map, int &ch
   else { map = 4; ch = has_vel ? c - 8 : c - 6; tcol = has_vel ? c : c + 2; }
 }
 __device__ __forceinline__ int channels_of(int map) { return map == 1 ? 1 : (map == 2 ? 3 : 2); }
-
-template <int IO>
-__device__ __forceinline__ float ld1(const void *base, int64_t e) {
-  if constexpr (IO == LINK_IO_F32) {
-    return reinterpret_cast<const float *>(base)[e];
-  } else if constexpr (IO == LINK_IO_F16) {
-    return (float)reinterpret_cast<const _Float16 *>(base)[e];
-  } else {
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[e] << 16);
-  }
-}
-
-template <int IO>
-__device__ __forceinline__ void st1(void *base, int64_t e, float v) {
-  if constexpr (IO == LINK_IO_F32) {
-    reinterpret_cast<float *>(base)[e] = v;
-  } else if constexpr (IO == LINK_IO_F16) {
-    reinterpret_cast<_Float16 *>(base)[e] = (_Float16)v;
-  } else {
-    reinterpret_cast<unsigned short *>(base)[e] = (unsigned short)bf16_rne(v);
-  }
-}
-
-// sum of v over the workgroup by a tree of fixed shape: the same bits whatever the schedule.  lds: >= 256 floats.
-__device__ __forceinline__ float block_sum_fixed(float v, float *lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = lds[t] + lds[t + s];
-    __syncthreads();
-  }
-  const float r = lds[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ int block_sum_int(int v, int *lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] += lds[t + s];
-    __syncthreads();
-  }
-  const int r = lds[0];
-  __syncthreads();
-  return r;
-}
 
 // ------------------------------------------------------------------------------------------------------------------- assign
 __global__ void __launch_bounds__(T) k_assign_clear(AssignPtrs P, int ntasks, int64_t total) {
@@ -294,7 +244,7 @@ __device__ __forceinline__ void neg_term(float x, float tg, int probas, float &v
 __device__ __forceinline__ int count_mask(const uint8_t *__restrict__ mask, int64_t n, int *lds) {
   int c = 0;
   for (int64_t i = threadIdx.x; i < n; i += T) c += mask[i] != 0;
-  return block_sum_int(c, lds);
+  return block_sum_fixed(c, lds);
 }
 
 template <int IO, bool VEC4>
@@ -325,7 +275,7 @@ __global__ void __launch_bounds__(T) k_loss_map(const void *__restrict__ hm, con
       const int64_t e = e0 + j;
       if (e < n) {
         float v, g;
-        neg_term(ld1<IO>(hm, e), target[e], probas, v, g);
+        neg_term(row_ld1<IO>(hm, e), target[e], probas, v, g);
         acc = j ? acc + v : v;
         unit_hm[e] = g * scale;
       }
@@ -367,7 +317,7 @@ __global__ void __launch_bounds__(T) k_loss_slots(const void *__restrict__ hm, R
         kk = (int)(ct * HW + id);
         if (has_hm) {
           float y, dydx;
-          activate(ld1<IO>(hm, (int64_t)b * K * HW + kk), probas, y, dydx);
+          activate(row_ld1<IO>(hm, (int64_t)b * K * HW + kk), probas, y, dydx);
           const float ly = logf(y), om = 1.0f - y;
           pos += ly * (om * om);
           gp = ((om * om) / y - 2.0f * om * ly) * dydx * hscale;
@@ -377,7 +327,7 @@ __global__ void __launch_bounds__(T) k_loss_slots(const void *__restrict__ hm, R
           if (has_reg && c < ncol) {
             int map, ch, tcol;
             column_of(c, has_vel != 0, map, ch, tcol);
-            const float pred = ld1<IO>(R.p[map], (int64_t)b * R.bs[map] + (int64_t)ch * HW + id);
+            const float pred = row_ld1<IO>(R.p[map], (int64_t)b * R.bs[map] + (int64_t)ch * HW + id);
             const float d = pred - anno[s * NCOL + tcol];
             box[c] += fabsf(d);
             u[c] = (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f)) * (Wt.cw[c] * bscale);
@@ -470,7 +420,7 @@ __global__ void __launch_bounds__(T) k_bwd_map(const float *__restrict__ unit_hm
       row_st4<IO>(grad_hm, e0, u);
     } else {
       for (int j = 0; j < VEC; ++j)
-        if (e0 + j < n) st1<IO>(grad_hm, e0 + j, unit_hm[e0 + j] * s);
+        if (e0 + j < n) row_st1<IO>(grad_hm, e0 + j, unit_hm[e0 + j] * s);
     }
     return;
   }
@@ -481,7 +431,7 @@ __global__ void __launch_bounds__(T) k_bwd_map(const float *__restrict__ unit_hm
       if (map == 3 && !has_vel) continue;
       const int64_t per = (int64_t)channels_of(map) * HW, sz = (int64_t)B * per;
       if (q < sz) {
-        st1<IO>(G.p[map], (q / per) * G.bs[map] + q % per, 0.f);
+        row_st1<IO>(G.p[map], (q / per) * G.bs[map] + q % per, 0.f);
         break;
       }
       q -= sz;
@@ -528,7 +478,7 @@ __global__ void __launch_bounds__(T) k_bwd_slots(const float *__restrict__ unit_
       if (c < ncol) {
         int map, ch, tcol;
         column_of(c, has_vel != 0, map, ch, tcol);
-        st1<IO>(G.p[map], (int64_t)b * G.bs[map] + (int64_t)ch * HW + kk, g[c] * up);
+        row_st1<IO>(G.p[map], (int64_t)b * G.bs[map] + (int64_t)ch * HW + kk, g[c] * up);
       }
     }
   }
@@ -545,8 +495,6 @@ inline bool loss_shape_ok(int32_t batch, int32_t k, int32_t h, int32_t w, int32_
 }
 
 inline int64_t map_blocks(int64_t n) { return (n + TILE - 1) / TILE; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -636,26 +584,20 @@ extern "C" int link_center_loss_forward(const void *hm, const void *reg, const v
   float *part = reinterpret_cast<float *>(workspace);
   float *fpart = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + up256((size_t)nblk * 4));
   const int probas = input_kind == LINK_CENTER_PROBAS, has_vel = vel != nullptr, HW = h * w;
-  const bool v4 = aligned16(hm) && aligned16(hm_target) && aligned16(unit_hm);
+  const bool v4 = aligned_to(hm, 16) && aligned_to(hm_target, 16) && aligned_to(unit_hm, 16);
   Weights Wt;
   for (int c = 0; c < NCOL; ++c) Wt.cw[c] = has_reg && c < (has_vel ? NCOL : NCOL - 2) ? code_weights[c] : 0.f;
   hipStream_t s = S(stream);
   const dim3 gm((unsigned)nblk), gb((unsigned)batch), tb(T);
-#define LINK_CL_FWD(IO)                                                                                                              \
-  do {                                                                                                                               \
-    if (hm && v4)                                                                                                                    \
-      hipLaunchKernelGGL((k_loss_map<IO, true>), gm, tb, 0, s, hm, hm_target, n, probas, mask, nmask, part, unit_hm);               \
-    else if (hm)                                                                                                                     \
-      hipLaunchKernelGGL((k_loss_map<IO, false>), gm, tb, 0, s, hm, hm_target, n, probas, mask, nmask, part, unit_hm);              \
-    hipLaunchKernelGGL(k_loss_slots<IO>, gb, tb, 0, s, hm, R, has_vel, probas, anno_box, ind, mask, cat, (int)batch, (int)k, HW,    \
-                       (int)max_objs, Wt, weight, fpart, unit_hm, unit_box);                                                         \
-  } while (0)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_CL_FWD(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_CL_FWD(LINK_IO_F16); break;
-    default: LINK_CL_FWD(LINK_IO_BF16);
-  }
-#undef LINK_CL_FWD
+  dispatch_row_io(io_dtype, [&](auto io) {
+    constexpr int IO = decltype(io)::value;
+    if (hm && v4)
+      hipLaunchKernelGGL((k_loss_map<IO, true>), gm, tb, 0, s, hm, hm_target, n, probas, mask, nmask, part, unit_hm);
+    else if (hm)
+      hipLaunchKernelGGL((k_loss_map<IO, false>), gm, tb, 0, s, hm, hm_target, n, probas, mask, nmask, part, unit_hm);
+    hipLaunchKernelGGL(k_loss_slots<IO>, gb, tb, 0, s, hm, R, has_vel, probas, anno_box, ind, mask, cat, (int)batch, (int)k, HW,
+                       (int)max_objs, Wt, weight, fpart, unit_hm, unit_box);
+  });
   hipLaunchKernelGGL(k_loss_final, dim3(1), tb, 0, s, part, hm ? nblk : (int64_t)0, fpart, (int)batch, mask, nmask, has_vel, Wt, weight, out);
   return check_launch("link_center_loss_forward");
 }
@@ -679,22 +621,16 @@ extern "C" int link_center_loss_backward(const float *unit_hm, const float *unit
   const int64_t nreg = has_reg ? (int64_t)batch * (has_vel ? NCOL : NCOL - 2) * HW : 0;      // batch * 3 * hw < 2^31: < 2^33
   const int64_t nblk_reg = map_blocks(nreg);
   if (nblk + nblk_reg >= (1LL << 31)) return LINK_ERR_ARG;
-  const bool v4 = aligned16(unit_hm) && aligned16(grad_hm);
+  const bool v4 = aligned_to(unit_hm, 16) && aligned_to(grad_hm, 16);
   hipStream_t s = S(stream);
   const dim3 gm((unsigned)(nblk + nblk_reg)), gb((unsigned)batch), tb(T);
-#define LINK_CL_BWD(IO)                                                                                                              \
-  do {                                                                                                                               \
-    if (v4)                                                                                                                          \
-      hipLaunchKernelGGL((k_bwd_map<IO, true>), gm, tb, 0, s, unit_hm, upstream, n, nblk, grad_hm, G, has_vel, (int)batch, HW);     \
-    else                                                                                                                             \
-      hipLaunchKernelGGL((k_bwd_map<IO, false>), gm, tb, 0, s, unit_hm, upstream, n, nblk, grad_hm, G, has_vel, (int)batch, HW);    \
-    if (has_reg) hipLaunchKernelGGL(k_bwd_slots<IO>, gb, tb, 0, s, unit_box, ind, mask, upstream, HW, (int)max_objs, G, has_vel);   \
-  } while (0)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_CL_BWD(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_CL_BWD(LINK_IO_F16); break;
-    default: LINK_CL_BWD(LINK_IO_BF16);
-  }
-#undef LINK_CL_BWD
+  dispatch_row_io(io_dtype, [&](auto io) {
+    constexpr int IO = decltype(io)::value;
+    if (v4)
+      hipLaunchKernelGGL((k_bwd_map<IO, true>), gm, tb, 0, s, unit_hm, upstream, n, nblk, grad_hm, G, has_vel, (int)batch, HW);
+    else
+      hipLaunchKernelGGL((k_bwd_map<IO, false>), gm, tb, 0, s, unit_hm, upstream, n, nblk, grad_hm, G, has_vel, (int)batch, HW);
+    if (has_reg) hipLaunchKernelGGL(k_bwd_slots<IO>, gb, tb, 0, s, unit_box, ind, mask, upstream, HW, (int)max_objs, G, has_vel);
+  });
   return check_launch("link_center_loss_backward");
 }

@@ -12,7 +12,7 @@
 #pragma clang fp contract(off)
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
 
 using namespace link;
 
@@ -160,20 +160,6 @@ __global__ __launch_bounds__(256) void k_box_collision(const float *__restrict__
 }
 
 // ---- P3: the sampler's acceptance scan ------------------------------------------------------------------------------------------
-// position of a flagged thread among the flagged threads of the workgroup, in thread order, and their number (uniform calls only)
-__device__ __forceinline__ int block_rank(bool flag, int *wsum, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
-  int base = 0;
-  for (int i = 0; i < w; i++) base += wsum[i];
-  total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return base + r;
-}
-
 // sample_ops.py:97-172 + 250-296 for one frame per workgroup.  The frame's avoid set -- the BEV corners of the surviving ground
 // truth, then of everything accepted -- lives in LDS (1024 x 8 floats), as do the corners of the class in hand (at most 64) and
 // its collision rows: one 64-bit word per candidate against its own class (a wave takes a row, a lane a column, the word is the

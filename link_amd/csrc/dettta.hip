@@ -61,10 +61,6 @@ __global__ __launch_bounds__(256) void k_tta_views(const float *__restrict__ pts
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------
-struct decode_geom {
-  float osf, vx, vy, px, py, thr, lo[3], hi[3];
-};
-
 // The mean of the four views: ((v0 + v1) + v2) + v3, then * 0.25 (exact: a power of two) -- the views in ascending order, which
 // is also the order a sequential sum over dim 1 of the reference's [B, 4, H, W, C] tensor takes.
 __device__ __forceinline__ float mean4(float a, float b, float c, float d) { return (((a + b) + c) + d) * 0.25f; }
@@ -127,17 +123,9 @@ __global__ __launch_bounds__(256) void k_center_decode_flip4(const float *__rest
   scores[f + cell] = ok ? best : -INFINITY;
 }
 
-// unmasked cells per frame: one workgroup per frame, integer sums through LDS (no atomics)
+// unmasked cells per frame (box_iou.h)
 __global__ __launch_bounds__(256) void k_tta_count(const float *__restrict__ scores, int hw, int32_t *__restrict__ counts) {
-  __shared__ int part[4];
-  const float *s = scores + (int64_t)blockIdx.x * hw;
-  int c = 0;
-  for (int i = threadIdx.x; i < hw; i += 256) c += s[i] > -INFINITY ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  center_count_frame(scores, hw, counts);
 }
 
 // ---- class-wise mask ------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,9 @@
 #pragma clang fp contract(off)
 #include <math.h>
 
+#include "block_prims.h"
 #include "box_iou.h"
+#include "dispatch.h"
 #include "row_io.h"
 
 using namespace link;
@@ -33,46 +35,8 @@ constexpr float TWO_PI_F = 6.28318530717958647692f;      // op sees of the refer
 constexpr float HALF_PI_F = 1.57079632679489661923f;
 constexpr float PI15_F = 4.71238898038468985769f;
 
-template <int IO>
-__device__ __forceinline__ float ld1(const void *base, int64_t e) {
-  if constexpr (IO == LINK_IO_F32) {
-    return reinterpret_cast<const float *>(base)[e];
-  } else if constexpr (IO == LINK_IO_F16) {
-    return (float)reinterpret_cast<const _Float16 *>(base)[e];
-  } else {
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[e] << 16);
-  }
-}
-
-template <int IO>
-__device__ __forceinline__ void st1(void *base, int64_t e, float v) {
-  if constexpr (IO == LINK_IO_F32) {
-    reinterpret_cast<float *>(base)[e] = v;
-  } else if constexpr (IO == LINK_IO_F16) {
-    reinterpret_cast<_Float16 *>(base)[e] = (_Float16)v;
-  } else {
-    reinterpret_cast<unsigned short *>(base)[e] = (unsigned short)bf16_rne(v);
-  }
-}
-
 __device__ __forceinline__ float cosd(float a) { return (float)cos((double)a); }       // correctly rounded, as box_iou.h's staging
 __device__ __forceinline__ float sind(float a) { return (float)sin((double)a); }
-
-// sum over the workgroup by a tree of fixed shape (centerloss.hip); lds: T entries
-template <typename V>
-__device__ __forceinline__ V block_sum_fixed(V v, V *lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = lds[t] + lds[t + s];
-    __syncthreads();
-  }
-  const V r = lds[0];
-  __syncthreads();
-  return r;
-}
 
 // ---- O1: features ---------------------------------------------------------------------------------------------------------------
 struct BevGeom {
@@ -88,7 +52,6 @@ __device__ __forceinline__ int floor_cell(float v, int n) {
   if (f >= (float)n) return n;
   return (int)f;
 }
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 template <int IO, bool VEC>
 __global__ __launch_bounds__(T) void k_roi_bev(const void *__restrict__ bev, BevGeom g, const float *__restrict__ boxes,
@@ -108,7 +71,7 @@ __global__ __launch_bounds__(T) void k_roi_bev(const void *__restrict__ bev, Bev
     if (VEC) {
       for (int c = lane * 4; c < g.C; c += 256) row_st4<IO>(out, o0 + c, make_float4(0.f, 0.f, 0.f, 0.f));
     } else {
-      for (int c = lane; c < g.C; c += 64) st1<IO>(out, o0 + c, 0.f);
+      for (int c = lane; c < g.C; c += 64) row_st1<IO>(out, o0 + c, 0.f);
     }
     return;
   }
@@ -129,7 +92,7 @@ __global__ __launch_bounds__(T) void k_roi_bev(const void *__restrict__ bev, Bev
   }
   const float fx = (x - g.px) / g.vx / g.os, fy = (y - g.py) / g.vy / g.os;    // absl_to_relative, every operation rounded
   const int xf = floor_cell(fx, g.W), yf = floor_cell(fy, g.H);
-  const int x0 = clampi(xf, g.W - 1), x1 = clampi(xf + 1, g.W - 1), y0 = clampi(yf, g.H - 1), y1 = clampi(yf + 1, g.H - 1);
+  const int x0 = clampi(xf, 0, g.W - 1), x1 = clampi(xf + 1, 0, g.W - 1), y0 = clampi(yf, 0, g.H - 1), y1 = clampi(yf + 1, 0, g.H - 1);
   // center_utils.py:116-119: the weights from the CLAMPED corners
   const float wa = ((float)x1 - fx) * ((float)y1 - fy), wb = ((float)x1 - fx) * (fy - (float)y0);
   const float wc = (fx - (float)x0) * ((float)y1 - fy), wd = (fx - (float)x0) * (fy - (float)y0);
@@ -149,8 +112,8 @@ __global__ __launch_bounds__(T) void k_roi_bev(const void *__restrict__ bev, Bev
   } else {
     for (int c = lane; c < g.C; c += 64) {
       const int64_t k = (int64_t)c * g.sc;
-      const float a = ld1<IO>(bev, ea + k), bq = ld1<IO>(bev, eb + k), cq = ld1<IO>(bev, ec + k), d = ld1<IO>(bev, ed + k);
-      st1<IO>(out, o0 + c, ((a * wa + bq * wb) + cq * wc) + d * wd);
+      const float a = row_ld1<IO>(bev, ea + k), bq = row_ld1<IO>(bev, eb + k), cq = row_ld1<IO>(bev, ec + k), d = row_ld1<IO>(bev, ed + k);
+      row_st1<IO>(out, o0 + c, ((a * wa + bq * wb) + cq * wc) + d * wd);
     }
   }
 }
@@ -450,7 +413,7 @@ __global__ __launch_bounds__(T) void k_roi_loss(const void *__restrict__ cls, co
     float g = 0.f;
     if (tg >= 0.f) {                                                            // a masked row is not read
       float v;
-      bce_term(ld1<IO>(cls, i), tg, v, g);
+      bce_term(row_ld1<IO>(cls, i), tg, v, g);
       sc = sc + v;
       g = g / vden * cls_weight;
     }
@@ -460,7 +423,7 @@ __global__ __launch_bounds__(T) void k_roi_loss(const void *__restrict__ cls, co
     for (int c = 0; c < code; c++) {
       float u = 0.f;
       if (on) {
-        const float d = ld1<IO>(reg, (int64_t)i * code + c) - gt_of_rois[(int64_t)i * ncol + c];
+        const float d = row_ld1<IO>(reg, (int64_t)i * code + c) - gt_of_rois[(int64_t)i * ncol + c];
         row = row + fabsf(d) * cw.w[c];
         u = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * cw.w[c] / fden * reg_weight;
       }
@@ -484,8 +447,8 @@ __global__ __launch_bounds__(T) void k_roi_loss_bwd(const float *__restrict__ un
                                                     void *__restrict__ grad_reg) {
   const int e = blockIdx.x * T + threadIdx.x;
   const float s = upstream[0];
-  if (e < n) st1<IO>(grad_cls, e, unit_cls[e] * s);
-  if (e < n * code) st1<IO>(grad_reg, e, unit_reg[e] * s);
+  if (e < n) row_st1<IO>(grad_cls, e, unit_cls[e] * s);
+  if (e < n * code) row_st1<IO>(grad_reg, e, unit_reg[e] * s);
 }
 
 // ---- O4: refine -------------------------------------------------------------------------------------------------------------------
@@ -513,7 +476,7 @@ __global__ __launch_bounds__(T) void k_roi_refine(const float *__restrict__ rois
     if (keep) {
       float roi[9], v[9];
       for (int c = 0; c < code; c++) roi[c] = rois[ri * code + c];
-      for (int c = 0; c < code; c++) v[c] = ld1<IO>(reg, ri * code + c) + (c < 3 ? 0.f : roi[c]);      // the ROI with its centre zeroed
+      for (int c = 0; c < code; c++) v[c] = row_ld1<IO>(reg, ri * code + c) + (c < 3 ? 0.f : roi[c]);      // the ROI with its centre zeroed
       const float ca = cosd(roi[6]), sa = sind(roi[6]);
       const float x = v[0], y = v[1];
       v[0] = (x * ca + y * sa) + roi[0];                                        // rotate_points_along_z, then the centre back
@@ -525,7 +488,7 @@ __global__ __launch_bounds__(T) void k_roi_refine(const float *__restrict__ rois
         v[6] = v[7]; v[7] = v[8]; v[8] = h;
       }
       for (int c = 0; c < code; c++) o_boxes[o * code + c] = v[c];
-      const float p = 1.0f / (1.0f + expf(-ld1<IO>(cls, ri)));
+      const float p = 1.0f / (1.0f + expf(-row_ld1<IO>(cls, ri)));
       o_scores[o] = sqrtf(p * roi_scores[ri]);
       o_labels[o] = lab - 1;
     }
@@ -543,7 +506,6 @@ __global__ __launch_bounds__(T) void k_roi_refine(const float *__restrict__ rois
   if (t == 0) counts[b] = kept;
 }
 
-inline bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline bool finite_pos(float v) { return isfinite(v) && v > 0.f; }
 
 }  // namespace
@@ -576,17 +538,11 @@ extern "C" int link_roi_bev_features(const void *bev, int32_t io_dtype, const in
                    aligned_to(out, vb);
   const dim3 grid(blocks_for(waves, T / 64)), block(T);
   const long long *lb = reinterpret_cast<const long long *>(labels);
-#define LINK_ROI_BEV(IO)                                                                                      \
-  do {                                                                                                        \
-    if (vec) hipLaunchKernelGGL((k_roi_bev<IO, true>), grid, block, 0, S(stream), bev, g, boxes, lb, sel, waves, out);  \
-    else hipLaunchKernelGGL((k_roi_bev<IO, false>), grid, block, 0, S(stream), bev, g, boxes, lb, sel, waves, out);     \
-  } while (0)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_ROI_BEV(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_ROI_BEV(LINK_IO_F16); break;
-    default: LINK_ROI_BEV(LINK_IO_BF16);
-  }
-#undef LINK_ROI_BEV
+  dispatch_row_io(io_dtype, [&](auto io) {
+    constexpr int IO = decltype(io)::value;
+    if (vec) hipLaunchKernelGGL((k_roi_bev<IO, true>), grid, block, 0, S(stream), bev, g, boxes, lb, sel, waves, out);
+    else hipLaunchKernelGGL((k_roi_bev<IO, false>), grid, block, 0, S(stream), bev, g, boxes, lb, sel, waves, out);
+  });
   return check_launch("link_roi_bev_features");
 }
 
@@ -639,15 +595,10 @@ extern "C" int link_roi_loss_forward(const void *rcnn_cls, const void *rcnn_reg,
   CodeW cw;
   for (int c = 0; c < 9; c++) cw.w[c] = c < code ? code_weights[c] : 0.f;
   const long long *rv = reinterpret_cast<const long long *>(reg_valid_mask);
-#define LINK_ROI_LOSS(IO)                                                                                                     \
-  hipLaunchKernelGGL(k_roi_loss<IO>, dim3(1), dim3(T), 0, S(stream), rcnn_cls, rcnn_reg, (int)n, (int)code, cls_labels, gt_of_rois, rv, \
-                     cw, cls_weight, reg_weight, out, unit_cls, unit_reg)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_ROI_LOSS(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_ROI_LOSS(LINK_IO_F16); break;
-    default: LINK_ROI_LOSS(LINK_IO_BF16);
-  }
-#undef LINK_ROI_LOSS
+  dispatch_row_io(io_dtype, [&](auto io) {
+    hipLaunchKernelGGL(k_roi_loss<decltype(io)::value>, dim3(1), dim3(T), 0, S(stream), rcnn_cls, rcnn_reg, (int)n, (int)code, cls_labels,
+                       gt_of_rois, rv, cw, cls_weight, reg_weight, out, unit_cls, unit_reg);
+  });
   return check_launch("link_roi_loss_forward");
 }
 
@@ -656,14 +607,10 @@ extern "C" int link_roi_loss_backward(const float *unit_cls, const float *unit_r
   if (!row_io_ok(io_dtype) || (code != 7 && code != 9) || n < 1 || n > LINK_ROI_MAX_LOSS_ROWS) return LINK_ERR_ARG;
   if (!unit_cls || !unit_reg || !upstream || !grad_cls || !grad_reg) return LINK_ERR_ARG;
   const dim3 grid(blocks_for(n * code, T)), block(T);
-#define LINK_ROI_BWD(IO) \
-  hipLaunchKernelGGL(k_roi_loss_bwd<IO>, grid, block, 0, S(stream), unit_cls, unit_reg, upstream, (int)n, (int)code, grad_cls, grad_reg)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_ROI_BWD(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_ROI_BWD(LINK_IO_F16); break;
-    default: LINK_ROI_BWD(LINK_IO_BF16);
-  }
-#undef LINK_ROI_BWD
+  dispatch_row_io(io_dtype, [&](auto io) {
+    hipLaunchKernelGGL(k_roi_loss_bwd<decltype(io)::value>, grid, block, 0, S(stream), unit_cls, unit_reg, upstream, (int)n, (int)code,
+                       grad_cls, grad_reg);
+  });
   return check_launch("link_roi_loss_backward");
 }
 
@@ -678,14 +625,9 @@ extern "C" int link_roi_refine(const float *rois, const int64_t *roi_labels, con
   if (r > 0 && (!rois || !roi_labels || !roi_scores || !rcnn_cls || !rcnn_reg || !boxes || !scores || !labels)) return LINK_ERR_ARG;
   const long long *lb = reinterpret_cast<const long long *>(roi_labels);
   long long *ol = reinterpret_cast<long long *>(labels);
-#define LINK_ROI_REFINE(IO)                                                                                                        \
-  hipLaunchKernelGGL(k_roi_refine<IO>, dim3(batch), dim3(T), 0, S(stream), rois, lb, roi_scores, rcnn_cls, rcnn_reg, (int)r, (int)code, \
-                     boxes, scores, ol, counts)
-  switch (io_dtype) {
-    case LINK_IO_F32: LINK_ROI_REFINE(LINK_IO_F32); break;
-    case LINK_IO_F16: LINK_ROI_REFINE(LINK_IO_F16); break;
-    default: LINK_ROI_REFINE(LINK_IO_BF16);
-  }
-#undef LINK_ROI_REFINE
+  dispatch_row_io(io_dtype, [&](auto io) {
+    hipLaunchKernelGGL(k_roi_refine<decltype(io)::value>, dim3(batch), dim3(T), 0, S(stream), rois, lb, roi_scores, rcnn_cls, rcnn_reg, (int)r,
+                       (int)code, boxes, scores, ol, counts);
+  });
   return check_launch("link_roi_refine");
 }

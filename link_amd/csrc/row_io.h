@@ -55,6 +55,31 @@ __device__ __forceinline__ void row_st4(void *base, int64_t e, float4 v) {
   }
 }
 
+// one element of a row, for the kernels that walk a row a scalar at a time
+template <int IO>
+__device__ __forceinline__ float row_ld1(const void *base, int64_t e) {
+  static_assert(IO == LINK_IO_F32 || IO == LINK_IO_F16 || IO == LINK_IO_BF16, "row type");
+  if constexpr (IO == LINK_IO_F32) {
+    return reinterpret_cast<const float *>(base)[e];
+  } else if constexpr (IO == LINK_IO_F16) {
+    return (float)reinterpret_cast<const _Float16 *>(base)[e];
+  } else {
+    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[e] << 16);
+  }
+}
+
+template <int IO>
+__device__ __forceinline__ void row_st1(void *base, int64_t e, float v) {
+  static_assert(IO == LINK_IO_F32 || IO == LINK_IO_F16 || IO == LINK_IO_BF16, "row type");
+  if constexpr (IO == LINK_IO_F32) {
+    reinterpret_cast<float *>(base)[e] = v;
+  } else if constexpr (IO == LINK_IO_F16) {
+    reinterpret_cast<_Float16 *>(base)[e] = (_Float16)v;
+  } else {
+    reinterpret_cast<unsigned short *>(base)[e] = (unsigned short)bf16_rne(v);
+  }
+}
+
 inline bool row_io_ok(int32_t io_dtype) {
   return io_dtype == LINK_IO_F32 || io_dtype == LINK_IO_F16 || io_dtype == LINK_IO_BF16;
 }

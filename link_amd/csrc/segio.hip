@@ -32,7 +32,9 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
+#include "dispatch.h"
+#include "radix_pass.h"
 #include "row_io.h"
 
 using namespace link;
@@ -42,7 +44,7 @@ namespace {
 constexpr int T = 256;                       // threads per workgroup (4 waves), every kernel here
 constexpr int ITEMS = 8;
 constexpr int TILE = T * ITEMS;              // pairs per sort tile and positions per scan tile
-static_assert(TILE == LINK_SEGQ_SORT_TILE, "the header names the tile");
+static_assert(T == RADIX_T && TILE == RADIX_TILE && TILE == LINK_SEGQ_SORT_TILE, "the header names the tile");
 constexpr int MAX_BATCH = 1024;
 constexpr int64_t MAX_POINTS = 1LL << 28;
 constexpr int MAX_NDIM = 16;
@@ -55,8 +57,6 @@ struct Layout {
   int64_t ntiles;
   size_t hdr, sinfo, voff, keys0, keys1, vals0, vals1, hist, bsum, total;
 };
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline bool shape_ok(int64_t n, int32_t batch) { return n >= 0 && n < MAX_POINTS && batch >= 1 && batch <= MAX_BATCH; }
 
@@ -78,44 +78,8 @@ Layout layout_of(int64_t n, int32_t batch) {
   return L;
 }
 
-// ------------------------------------------------------------------------------------------------------------ block helpers
-// exclusive prefix of v over the workgroup's 256 threads in thread order; total = the workgroup's sum.  lds: >= 4 ints.
-__device__ __forceinline__ int block_scan_excl(int v, int *lds, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();                                                  // lds may still be read from an earlier call
-  if (lane == 63) lds[w] = x;
-  __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < T / 64; ++i) {
-    const int s = lds[i];
-    if (i < w) woff += s;
-    tot += s;
-  }
-  total = tot;
-  return woff + x - v;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // the number of points: point_offsets[batch], clamped to the capacity
 __device__ __forceinline__ int sq_points(const int32_t *__restrict__ po, int batch, int64_t n) { return clampi(po[batch], 0, (int)n); }
-
-// the sample of point i: the last b with point_offsets[b] <= i (b = 0 when there is none)
-__device__ __forceinline__ int sq_sample(const int32_t *__restrict__ po, int batch, int i) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (po[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ int bits_of(uint32_t v) { return v == 0 ? 0 : 32 - __clz((int)v); }
 
@@ -158,7 +122,7 @@ __global__ void __launch_bounds__(T) k_sq_minmax(const void *__restrict__ pts, i
   const bool in = i < npts;
   int b = -1, flags = 0, q[3] = {0, 0, 0};
   if (in) {
-    b = sq_sample(po, batch, (int)i);
+    b = sample_of_point(po, batch, (int)i);
     flags = sq_coord(pts, mode, ndim, vs, i, q);
   }
   const bool good = in && flags == 0;
@@ -256,7 +220,7 @@ __global__ void __launch_bounds__(T) k_sq_keys(const void *__restrict__ pts, int
   const int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
   if (i >= hdr[H_NPTS]) return;
   const int wy = hdr[H_WY], wz = hdr[H_WZ], sb = hdr[H_WX] + wy + wz;                 // sb <= 60
-  const int b = sq_sample(po, batch, (int)i);
+  const int b = sample_of_point(po, batch, (int)i);
   const int *s = sinfo + b * S_WORDS;
   uint64_t key = (uint64_t)b << sb;
   if (s[S_OK]) {
@@ -269,108 +233,26 @@ __global__ void __launch_bounds__(T) k_sq_keys(const void *__restrict__ pts, int
   vals[i] = (uint32_t)i;
 }
 
-// hist[tile * 256 + digit]; every tile of a pass that runs writes its 256 words (zeros past the points)
+// One pass of radix_pass.h over the one segment of npts pairs: hist[tile * 256 + digit].  A pass whose digit lies above every key
+// does nothing (uniform: all three kernels read the same word).
 __global__ void __launch_bounds__(T) k_sq_hist(const uint64_t *__restrict__ keys, const int *__restrict__ hdr, int shift,
                                                uint32_t *__restrict__ hist) {
-  __shared__ int lh[256];
-  if (shift >= hdr[H_NBITS]) return;                                // uniform: the digit lies above every key
-  const int t = threadIdx.x;
-  const int64_t nv = hdr[H_NPTS], p0 = (int64_t)blockIdx.x * TILE;
-  lh[t] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < ITEMS; ++r) {
-    const int64_t p = p0 + r * T + t;
-    if (p < nv) atomicAdd(&lh[(int)((keys[p] >> shift) & 255u)], 1);
-  }
-  __syncthreads();
-  hist[(int64_t)blockIdx.x * 256 + t] = (uint32_t)lh[t];
-}
-
-// one workgroup, one thread per digit: where each (digit, tile) starts, in place
-__global__ void __launch_bounds__(T) k_sq_hist_scan(uint32_t *__restrict__ hist, int64_t ntiles, const int *__restrict__ hdr, int shift) {
-  __shared__ int il[8];
   if (shift >= hdr[H_NBITS]) return;
-  const int t = threadIdx.x;
-  uint32_t *h = hist + t;
-  int mine = 0;
-  for (int64_t t0 = 0; t0 < ntiles; t0 += 8) {
-    int v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t0 + j < ntiles ? (int)h[(t0 + j) * 256] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) mine += v[j];
-  }
-  int all;
-  int run = block_scan_excl(mine, il, all);
-  for (int64_t t0 = 0; t0 < ntiles; t0 += 8) {
-    int v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t0 + j < ntiles ? (int)h[(t0 + j) * 256] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (t0 + j < ntiles) h[(t0 + j) * 256] = (uint32_t)run;
-      run += v[j];
-    }
-  }
+  radix_tile_hist(keys, (int64_t)hdr[H_NPTS], (int64_t)blockIdx.x, shift, hist + (int64_t)blockIdx.x * 256);
 }
 
-// stable scatter of one tile.  Rounds run in position order; inside a round the rank of a key among the equal digits of its wave
-// comes from eight ballots, and the waves are chained through LDS in wave order.
+__global__ void __launch_bounds__(T) k_sq_hist_scan(uint32_t *__restrict__ hist, int64_t ntiles, const int *__restrict__ hdr, int shift) {
+  if (shift >= hdr[H_NBITS]) return;
+  radix_digit_scan(hist, ntiles);
+}
+
 __global__ void __launch_bounds__(T) k_sq_scatter(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                   const int *__restrict__ hdr, int shift, const uint32_t *__restrict__ hist,
                                                   uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out) {
-  __shared__ int base[256];
-  __shared__ int wcnt[T / 64][256];
   if (shift >= hdr[H_NBITS]) return;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t nv = hdr[H_NPTS], p0 = (int64_t)blockIdx.x * TILE;
-  if (p0 >= nv) return;                                             // uniform over the workgroup
-  base[t] = (int)hist[(int64_t)blockIdx.x * 256 + t];
-#pragma unroll
-  for (int i = 0; i < T / 64; ++i) wcnt[i][t] = 0;
-  __syncthreads();
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int r = 0; r < ITEMS; ++r) {
-    const int64_t p = p0 + r * T + t;
-    const bool act = p < nv;
-    uint64_t key = 0;
-    uint32_t val = 0;
-    if (act) {
-      key = keys[p];
-      val = vals[p];
-    }
-    const uint32_t d = (uint32_t)(key >> shift) & 255u;
-    unsigned long long same = __ballot(act);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long m = __ballot(act && bit);
-      same &= bit ? m : ~m;
-    }
-    const int rank = __popcll(same & lt);
-    if (act && rank == 0) wcnt[w][d] = __popcll(same);
-    __syncthreads();
-    if (act) {
-      int off = base[d] + rank;
-      for (int i = 0; i < w; ++i) off += wcnt[i][d];
-      if (off >= 0 && off < nv) {                                   // holds by construction; never write outside the pairs
-        keys_out[off] = key;
-        vals_out[off] = val;
-      }
-    }
-    __syncthreads();
-    {
-      int s = 0;
-#pragma unroll
-      for (int i = 0; i < T / 64; ++i) {
-        s += wcnt[i][t];
-        wcnt[i][t] = 0;
-      }
-      base[t] += s;
-    }
-    __syncthreads();
-  }
+  const int64_t nv = hdr[H_NPTS], tile = blockIdx.x;
+  if (tile * TILE >= nv) return;                                    // uniform over the workgroup
+  radix_tile_scatter(keys, vals, nv, tile, shift, hist + tile * 256, keys_out, vals_out);
 }
 
 // the buffer the last pass that ran wrote: passes alternate 0 -> 1 -> 0 ...
@@ -523,17 +405,6 @@ __global__ void __launch_bounds__(T) k_sq_tail(const int *__restrict__ hdr, int6
 }
 
 // ------------------------------------------------------------------------------------------------------------ vote and count
-template <int IO>
-__device__ __forceinline__ float ld1(const void *base, int64_t e) {
-  if constexpr (IO == LINK_IO_F32) {
-    return reinterpret_cast<const float *>(base)[e];
-  } else if constexpr (IO == LINK_IO_F16) {
-    return (float)reinterpret_cast<const _Float16 *>(base)[e];
-  } else {
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[e] << 16);
-  }
-}
-
 // IO = LINK_IO_*: rows of logits; IO = -1: int64 predictions
 template <int IO>
 __global__ void __launch_bounds__(T) k_vote_eval(const void *__restrict__ rows, int64_t n_rows, int c, const int32_t *__restrict__ inverse,
@@ -559,7 +430,7 @@ __global__ void __launch_bounds__(T) k_vote_eval(const void *__restrict__ rows, 
         const int64_t e0 = row * c;
 #pragma unroll
         for (int j = 0; j < LINK_SEGLOSS_MAX_CLASSES; ++j)
-          if (j < c) acc[j] += ld1<IO>(rows, e0 + j);
+          if (j < c) acc[j] += row_ld1<IO>(rows, e0 + j);
       }
       float best = -INFINITY;                                        // a NaN sum compares false: it counts as -inf and never wins
       int bi = 0;
@@ -661,19 +532,10 @@ extern "C" int link_seg_vote_eval(const void *rows, int32_t io_dtype, int32_t in
   if (input_kind == LINK_SEGEVAL_PREDICTIONS) {
     hipLaunchKernelGGL(k_vote_eval<-1>, g, dim3(T), 0, s, rows, n_rows, (int)c, inverse, 1, n_points, labels, ignore_label, lut, pred, cnt);
   } else {
-    switch (io_dtype) {
-      case LINK_IO_F32:
-        hipLaunchKernelGGL(k_vote_eval<LINK_IO_F32>, g, dim3(T), 0, s, rows, n_rows, (int)c, inverse, (int)votes, n_points, labels,
-                           ignore_label, lut, pred, cnt);
-        break;
-      case LINK_IO_F16:
-        hipLaunchKernelGGL(k_vote_eval<LINK_IO_F16>, g, dim3(T), 0, s, rows, n_rows, (int)c, inverse, (int)votes, n_points, labels,
-                           ignore_label, lut, pred, cnt);
-        break;
-      default:
-        hipLaunchKernelGGL(k_vote_eval<LINK_IO_BF16>, g, dim3(T), 0, s, rows, n_rows, (int)c, inverse, (int)votes, n_points, labels,
-                           ignore_label, lut, pred, cnt);
-    }
+    dispatch_row_io(io_dtype, [&](auto io) {
+      hipLaunchKernelGGL(k_vote_eval<decltype(io)::value>, g, dim3(T), 0, s, rows, n_rows, (int)c, inverse, (int)votes, n_points, labels,
+                         ignore_label, lut, pred, cnt);
+    });
   }
   return check_launch("link_seg_vote_eval");
 }

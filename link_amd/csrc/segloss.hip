@@ -26,7 +26,9 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
+#include "dispatch.h"
+#include "radix_pass.h"
 #include "row_io.h"
 
 using namespace link;
@@ -44,8 +46,6 @@ struct Layout {
   int64_t nrb, ntiles;
   size_t hdr, P, keys0, keys1, vals0, vals1, hist, rowcnt, cepart, cf, lpart, total;
 };
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline bool shape_ok(int64_t n, int32_t c) {
   // n is bounded before the product is formed: n * c cannot overflow
@@ -74,67 +74,6 @@ Layout layout_of(int64_t n, int32_t c) {
   return L;
 }
 
-// ------------------------------------------------------------------------------------------------------------ block helpers
-// exclusive prefix of v over the workgroup's 256 threads in thread order; total = the workgroup's sum.  lds: >= 4 ints.
-__device__ __forceinline__ int block_scan_excl(int v, int *lds, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[w] = x;
-  __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < T / 64; ++i) {
-    const int s = lds[i];
-    if (i < w) woff += s;
-    tot += s;
-  }
-  __syncthreads();
-  total = tot;
-  return woff + x - v;
-}
-
-// sum of v over the workgroup by a tree of fixed shape: the same bits whatever the schedule.  lds: >= 256 floats.
-__device__ __forceinline__ float block_sum_fixed(float v, float *lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = lds[t] + lds[t + s];
-    __syncthreads();
-  }
-  const float r = lds[0];
-  __syncthreads();
-  return r;
-}
-
-template <int IO>
-__device__ __forceinline__ float ld1(const void *base, int64_t e) {
-  if constexpr (IO == LINK_IO_F32) {
-    return reinterpret_cast<const float *>(base)[e];
-  } else if constexpr (IO == LINK_IO_F16) {
-    return (float)reinterpret_cast<const _Float16 *>(base)[e];
-  } else {
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[e] << 16);
-  }
-}
-
-template <int IO>
-__device__ __forceinline__ void st1(void *base, int64_t e, float v) {
-  if constexpr (IO == LINK_IO_F32) {
-    reinterpret_cast<float *>(base)[e] = v;
-  } else if constexpr (IO == LINK_IO_F16) {
-    reinterpret_cast<_Float16 *>(base)[e] = (_Float16)v;
-  } else {
-    reinterpret_cast<unsigned short *>(base)[e] = (unsigned short)bf16_rne(v);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ row pass
 template <int IO>
 __global__ void __launch_bounds__(T) k_rows(const void *__restrict__ rows, const int64_t *__restrict__ labels, int64_t n, int c,
@@ -158,16 +97,16 @@ __global__ void __launch_bounds__(T) k_rows(const void *__restrict__ rows, const
     valid = !use_lov_ignore || y != lov_ignore;
     const int64_t r0 = i * c;
     if (probas) {
-      for (int j = 0; j < c; ++j) P[(int64_t)j * n + i] = ld1<IO>(rows, r0 + j);
+      for (int j = 0; j < c; ++j) P[(int64_t)j * n + i] = row_ld1<IO>(rows, r0 + j);
     } else {
       float m = -INFINITY;
-      for (int j = 0; j < c; ++j) m = fmaxf(m, ld1<IO>(rows, r0 + j));
+      for (int j = 0; j < c; ++j) m = fmaxf(m, row_ld1<IO>(rows, r0 + j));
       float s = 0.f;
-      for (int j = 0; j < c; ++j) s += expf(ld1<IO>(rows, r0 + j) - m);
+      for (int j = 0; j < c; ++j) s += expf(row_ld1<IO>(rows, r0 + j) - m);
       const float inv = 1.0f / s;
-      for (int j = 0; j < c; ++j) P[(int64_t)j * n + i] = expf(ld1<IO>(rows, r0 + j) - m) * inv;
+      for (int j = 0; j < c; ++j) P[(int64_t)j * n + i] = expf(row_ld1<IO>(rows, r0 + j) - m) * inv;
       ce_on = in_range && y != ce_ignore;
-      if (ce_on) ce = logf(s) - (ld1<IO>(rows, r0 + y) - m);
+      if (ce_on) ce = logf(s) - (row_ld1<IO>(rows, r0 + y) - m);
     }
     if (valid && in_range) atomicAdd(&lh[(int)y], 1);
   }
@@ -243,112 +182,30 @@ __global__ void __launch_bounds__(T) k_keys(const int64_t *__restrict__ labels, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- radix sort
-// grid (ntiles, C).  hist[(class * ntiles + tile) * 256 + digit]: a tile's 256 words are contiguous, so this kernel's store, the scan's
-// loads (one thread per digit) and the scatter's load are coalesced; every tile writes its words (zeros past n_valid).
+// One pass of radix_pass.h over all C segments at once: grid (ntiles, C) for the tiles, grid C for the scan.  Segment c of the keys and
+// values starts at c * n and holds n_valid pairs; its histogram words are hist[(c * ntiles + tile) * 256 + digit].
+static_assert(T == RADIX_T && TILE == RADIX_TILE, "the sort tile is the finish chunk");
+
 __global__ void __launch_bounds__(T) k_hist(const uint32_t *__restrict__ keys, int64_t n, int64_t ntiles, const int *__restrict__ hdr,
                                             int shift, uint32_t *__restrict__ hist) {
-  __shared__ int lh[256];
-  const int t = threadIdx.x, cls = blockIdx.y;
+  const int cls = blockIdx.y;
   const int64_t tile = blockIdx.x;
-  const int64_t nv = hdr[H_NV];
-  lh[t] = 0;
-  __syncthreads();
-  const int64_t p0 = tile * TILE;
-  const uint32_t *k = keys + (int64_t)cls * n;
-#pragma unroll
-  for (int r = 0; r < ITEMS; ++r) {
-    const int64_t p = p0 + r * T + t;
-    if (p < nv) atomicAdd(&lh[(k[p] >> shift) & 255u], 1);
-  }
-  __syncthreads();
-  hist[((int64_t)cls * ntiles + tile) * 256 + t] = (uint32_t)lh[t];
+  radix_tile_hist(keys + (int64_t)cls * n, (int64_t)hdr[H_NV], tile, shift, hist + ((int64_t)cls * ntiles + tile) * 256);
 }
 
-// grid C, one thread per digit: where each (digit, tile) of the class starts, in place -- the keys of smaller digits first, then the
-// digit's own keys in the tiles before this one.  Loads are issued eight tiles at a time so their latencies overlap.
 __global__ void __launch_bounds__(T) k_hist_scan(uint32_t *__restrict__ hist, int64_t ntiles) {
-  __shared__ int il[8];
-  const int t = threadIdx.x;
-  uint32_t *h = hist + (int64_t)blockIdx.x * ntiles * 256 + t;
-  int mine = 0;
-  for (int64_t t0 = 0; t0 < ntiles; t0 += 8) {
-    int v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t0 + j < ntiles ? (int)h[(t0 + j) * 256] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) mine += v[j];
-  }
-  int all;
-  int run = block_scan_excl(mine, il, all);
-  for (int64_t t0 = 0; t0 < ntiles; t0 += 8) {
-    int v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t0 + j < ntiles ? (int)h[(t0 + j) * 256] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (t0 + j < ntiles) h[(t0 + j) * 256] = (uint32_t)run;
-      run += v[j];
-    }
-  }
+  radix_digit_scan(hist + (int64_t)blockIdx.x * ntiles * 256, ntiles);
 }
 
-// grid (ntiles, C): stable scatter of one tile.  Rounds run in position order; inside a round the rank of a key among the equal
-// digits of its wave comes from eight ballots, and the waves are chained through LDS in wave order.
 __global__ void __launch_bounds__(T) k_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n,
                                                int64_t ntiles, const int *__restrict__ hdr, int shift, const uint32_t *__restrict__ hist,
                                                uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out) {
-  __shared__ int base[256];
-  __shared__ int wcnt[T / 64][256];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, cls = blockIdx.y;
+  const int cls = blockIdx.y;
   const int64_t tile = blockIdx.x;
   const int64_t nv = hdr[H_NV];
-  const int64_t p0 = tile * TILE;
-  if (p0 >= nv) return;                                          // uniform over the workgroup
-  base[t] = (int)hist[((int64_t)cls * ntiles + tile) * 256 + t];
-#pragma unroll
-  for (int i = 0; i < T / 64; ++i) wcnt[i][t] = 0;
-  __syncthreads();
+  if (tile * TILE >= nv) return;                                 // uniform over the workgroup
   const int64_t seg = (int64_t)cls * n;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int r = 0; r < ITEMS; ++r) {
-    const int64_t p = p0 + r * T + t;
-    const bool act = p < nv;
-    uint32_t key = 0, val = 0;
-    if (act) {
-      key = keys[seg + p];
-      val = vals[seg + p];
-    }
-    const uint32_t d = (key >> shift) & 255u;
-    unsigned long long same = __ballot(act);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long m = __ballot(act && bit);
-      same &= bit ? m : ~m;
-    }
-    const int rank = __popcll(same & lt);
-    if (act && rank == 0) wcnt[w][d] = __popcll(same);
-    __syncthreads();
-    if (act) {
-      int off = base[d] + rank;
-      for (int i = 0; i < w; ++i) off += wcnt[i][d];
-      if (off >= 0 && off < nv) {                                // holds by construction; never write outside the segment
-        keys_out[seg + off] = key;
-        vals_out[seg + off] = val;
-      }
-    }
-    __syncthreads();
-    {
-      int s = 0;
-#pragma unroll
-      for (int i = 0; i < T / 64; ++i) {
-        s += wcnt[i][t];
-        wcnt[i][t] = 0;
-      }
-      base[t] += s;
-    }
-    __syncthreads();
-  }
+  radix_tile_scatter(keys + seg, vals + seg, nv, tile, shift, hist + ((int64_t)cls * ntiles + tile) * 256, keys_out + seg, vals_out + seg);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- finish
@@ -493,7 +350,7 @@ __global__ void __launch_bounds__(T) k_backward(const float *__restrict__ unit, 
   const int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
   if (i >= n) return;
   const float s = upstream[0];
-  for (int j = 0; j < c; ++j) st1<IO>(grad_rows, i * c + j, unit[(int64_t)j * n + i] * s);
+  for (int j = 0; j < c; ++j) row_st1<IO>(grad_rows, i * c + j, unit[(int64_t)j * n + i] * s);
 }
 
 }  // namespace
@@ -532,19 +389,10 @@ extern "C" int link_segloss_forward(const void *rows, int32_t io_dtype, int32_t 
     set_error("link_segloss_forward: memset", me);
     return LINK_ERR_LAUNCH;
   }
-  switch (io_dtype) {
-    case LINK_IO_F32:
-      hipLaunchKernelGGL(k_rows<LINK_IO_F32>, rb, dim3(T), 0, s, rows, labels, n, (int)c, probas, ce_ignore, lov_ignore, use_ign, P, hdr,
-                         rowcnt, cepart);
-      break;
-    case LINK_IO_F16:
-      hipLaunchKernelGGL(k_rows<LINK_IO_F16>, rb, dim3(T), 0, s, rows, labels, n, (int)c, probas, ce_ignore, lov_ignore, use_ign, P, hdr,
-                         rowcnt, cepart);
-      break;
-    default:
-      hipLaunchKernelGGL(k_rows<LINK_IO_BF16>, rb, dim3(T), 0, s, rows, labels, n, (int)c, probas, ce_ignore, lov_ignore, use_ign, P, hdr,
-                         rowcnt, cepart);
-  }
+  dispatch_row_io(io_dtype, [&](auto io) {
+    hipLaunchKernelGGL(k_rows<decltype(io)::value>, rb, dim3(T), 0, s, rows, labels, n, (int)c, probas, ce_ignore, lov_ignore, use_ign, P,
+                       hdr, rowcnt, cepart);
+  });
   hipLaunchKernelGGL(k_prefix, dim3(1), dim3(T), 0, s, hdr, rowcnt, cepart, L.nrb, (int)c, all);
   hipLaunchKernelGGL(k_keys, rb, dim3(T), 0, s, labels, n, (int)c, lov_ignore, use_ign, P, hdr, rowcnt, keys[0], vals[0]);
   for (int pass = 0; pass < 4; ++pass) {
@@ -566,10 +414,8 @@ extern "C" int link_segloss_backward(const float *unit_grad, const float *upstre
   if (!unit_grad || !upstream || !grad_rows || !shape_ok(n, c) || !row_io_ok(io_dtype)) return LINK_ERR_ARG;
   const dim3 rb((unsigned)(n > 0 ? (n + T - 1) / T : 1));
   hipStream_t s = S(stream);
-  switch (io_dtype) {
-    case LINK_IO_F32: hipLaunchKernelGGL(k_backward<LINK_IO_F32>, rb, dim3(T), 0, s, unit_grad, upstream, n, (int)c, grad_rows); break;
-    case LINK_IO_F16: hipLaunchKernelGGL(k_backward<LINK_IO_F16>, rb, dim3(T), 0, s, unit_grad, upstream, n, (int)c, grad_rows); break;
-    default: hipLaunchKernelGGL(k_backward<LINK_IO_BF16>, rb, dim3(T), 0, s, unit_grad, upstream, n, (int)c, grad_rows);
-  }
+  dispatch_row_io(io_dtype, [&](auto io) {
+    hipLaunchKernelGGL(k_backward<decltype(io)::value>, rb, dim3(T), 0, s, unit_grad, upstream, n, (int)c, grad_rows);
+  });
   return check_launch("link_segloss_backward");
 }

@@ -14,7 +14,7 @@
 #pragma clang fp contract(off)
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
 
 using namespace link;
 
@@ -55,25 +55,6 @@ struct TrackArgs {
   int32_t n, c, labels64;
   link_track_cfg_t cfg;
 };
-
-// exclusive rank of the threads with p among the workgroup, and their number (every thread of the workgroup calls it)
-__device__ __forceinline__ int block_rank(bool p, int *s_w, int &total) {
-  const uint64_t m = __ballot(p);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  __syncthreads();                             // the last call's readers are done with s_w
-  if (lane == 0) s_w[w] = __popcll(m);
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) {
-    const int v = s_w[i];
-    if (i < w) base += v;
-    tot += v;
-  }
-  total = tot;
-  return base + r;
-}
 
 // minimum of a 64-bit key over the wave, in every lane: four DPP steps inside each row of 16 lanes (lane ^ 1, lane ^ 2, the mirror of
 // the half row, the mirror of the row), then the four rows' results through readlane.  A lane whose DPP source is switched off keeps
@@ -174,7 +155,7 @@ __global__ __launch_bounds__(TB) void k_track_step(const TrackArgs a) {
       }
     }
     int tot;
-    const int r = block_rank(tl >= 0, s_w, tot);
+    const int r = block_rank<TB>(tl >= 0, s_w, tot);
     if (tl >= 0) {
       const int q = nd + r;
       double ct[2], tr[2];
@@ -277,8 +258,8 @@ __global__ __launch_bounds__(TB) void k_track_step(const TrackArgs a) {
     const bool ism = valid && j >= 0;
     const bool isn = valid && j < 0 && (no_th || scores[dslot[q]] > th);
     int tm, tn;
-    block_rank(ism, s_w, tm);
-    block_rank(isn, s_w, tn);
+    block_rank<TB>(ism, s_w, tm);
+    block_rank<TB>(isn, s_w, tn);
     nm += tm;
     nn += tn;
   }
@@ -291,8 +272,8 @@ __global__ __launch_bounds__(TB) void k_track_step(const TrackArgs a) {
     const bool ism = valid && j >= 0;
     const bool isn = valid && j < 0 && (no_th || scores[slot] > th);
     int tm, tn;
-    const int rm = block_rank(ism, s_w, tm);
-    const int rn = block_rank(isn, s_w, tn);
+    const int rm = block_rank<TB>(ism, s_w, tm);
+    const int rn = block_rank<TB>(isn, s_w, tn);
     if (ism || isn) {
       const int pos = ism ? bm + rm : nm + bn + rn;      // < nd <= N <= K
       double ct[2], tr[2];
@@ -319,7 +300,7 @@ __global__ __launch_bounds__(TB) void k_track_step(const TrackArgs a) {
     const int j = base + tid;
     const bool car = j < M && tmatch[j] < 0 && cur.age[j] < a.cfg.max_age;
     int tc;
-    const int rc = block_rank(car, s_w, tc);
+    const int rc = block_rank<TB>(car, s_w, tc);
     const int pos = nm + nn + bc + rc;
     if (car && pos < K) {
       nxt.ct[2 * pos] = cur.ct[2 * j] - cur.tr[2 * j];

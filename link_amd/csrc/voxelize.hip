@@ -17,7 +17,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "block_prims.h"
 
 using namespace link;
 
@@ -90,29 +90,6 @@ vx_layout vx_lay(int64_t cells_pad, int64_t ncap, int32_t batch) {
 }
 
 // ---- exclusive scan of int32 entries (MODE 1: of the popcounts of 32-bit words), three launches, any length below 2^31 ----
-__device__ __forceinline__ int wave_incl_scan(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of v over the 256 lanes of the workgroup; total = the sum over all of them
-__device__ __forceinline__ int block_excl_scan(int v, int *s_part /* [4] */, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(v, lane);
-  __syncthreads();                                                      // s_part may still be read from an earlier call
-  if (lane == 63) s_part[w] = inc;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) base += k < w ? s_part[k] : 0;
-  total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-  return base + inc - v;
-}
-
 template <int MODE>
 __device__ __forceinline__ int scan_entry(const int *__restrict__ in, int64_t i, int64_t n) {
   if (i >= n) return 0;
@@ -128,7 +105,7 @@ __global__ __launch_bounds__(256) void k_vx_scan_sum(const int *__restrict__ in,
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; k++) v += scan_entry<MODE>(in, base + k, n);
   int total;
-  block_excl_scan(v, s_part, total);
+  block_scan_excl(v, s_part, total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -139,7 +116,7 @@ __global__ __launch_bounds__(256) void k_vx_scan_top(int *__restrict__ bsum, int
   int v = 0;
   for (int k = 0; k < per; k++) v += b0 + k < nb ? bsum[b0 + k] : 0;
   int total;
-  int run = block_excl_scan(v, s_part, total);
+  int run = block_scan_excl(v, s_part, total);
   for (int k = 0; k < per && b0 + k < nb; k++) {
     const int x = bsum[b0 + k];
     bsum[b0 + k] = run;
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(256) void k_vx_scan_down(const int *in, int64_t n, 
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; k++) { x[k] = scan_entry<MODE>(in, base + k, n); v += x[k]; }
   int total;
-  int run = block_excl_scan(v, s_part, total) + bsum[blockIdx.x];
+  int run = block_scan_excl(v, s_part, total) + bsum[blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; k++) {
     if (base + k < n) out[base + k] = run;
@@ -174,18 +151,7 @@ int vx_scan(const int *in, int *out, int64_t n, int *bsum, hipStream_t st) {
 }
 
 // ---- the pipeline ----
-__device__ __forceinline__ int vx_clamp(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
-__device__ __forceinline__ int vx_points(const int32_t *__restrict__ po, const vx_geom &g) { return vx_clamp(po[g.batch], g.ncap); }
-
-// the sample of point i: the last b with point_offsets[b] <= i
-__device__ __forceinline__ int vx_sample(const int32_t *__restrict__ po, int batch, int i) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (po[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+__device__ __forceinline__ int vx_points(const int32_t *__restrict__ po, const vx_geom &g) { return clampi(po[g.batch], 0, g.ncap); }
 
 // Point pass: the cell of every point, its bit in the bitmap; the per-call records are reset on the way.  A coordinate that is not
 // finite fails the range test (every comparison with a NaN is false, an infinity is outside) and is never converted or indexed with.
@@ -220,7 +186,7 @@ __global__ __launch_bounds__(256) void k_vx_mark(const float *__restrict__ pts, 
       c[d] = ok ? (int)f : 0;
     }
     if (ok) {
-      const int b = vx_sample(po, g.batch, i);
+      const int b = sample_of_point(po, g.batch, i);
       cell = (uint32_t)b * g.cells_pad + (uint32_t)((c[2] * g.t[1] + c[1]) * g.t[0] + c[0]);
       atomicOr(&bitmap[cell >> 5], 1u << (cell & 31));
     }
@@ -270,8 +236,8 @@ __global__ __launch_bounds__(256) void k_vx_offsets(const int32_t *__restrict__ 
   for (int b = threadIdx.x; b < g.batch; b += 256) {
     int c;
     if (g.mode == LINK_VOXELIZE_HARD) {
-      const int s = vx_clamp(po[b], g.ncap);
-      int e = vx_clamp(po[b + 1], g.ncap);
+      const int s = clampi(po[b], 0, g.ncap);
+      int e = clampi(po[b + 1], 0, g.ncap);
       if (e < s) e = s;
       c = frank[e] - frank[s];
       if (c > g.max_voxels) c = g.max_voxels;
@@ -311,8 +277,8 @@ __global__ __launch_bounds__(256) void k_vx_assign(const int32_t *__restrict__ p
   cg[r] = pcell[i];
   int64_t v;
   if (g.mode == LINK_VOXELIZE_HARD) {
-    const int b = vx_sample(po, g.batch, i);
-    const int local = frank[i] - frank[vx_clamp(po[b], g.ncap)];
+    const int b = sample_of_point(po, g.batch, i);
+    const int local = frank[i] - frank[clampi(po[b], 0, g.ncap)];
     if (local < 0 || local >= g.max_voxels) return;                      // a cell past the first max_voxels: all its points are dropped
     v = (int64_t)voff[b] + local;
   } else {

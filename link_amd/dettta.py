@@ -31,17 +31,6 @@ def _cos_sin(angle: float):
     return float(np.float32(np.cos(np.float64(angle)))), float(np.float32(np.sin(np.float64(angle))))
 
 
-def _device_offsets(device, sizes):
-    """int32 [B + 1] on the device; kept per tuple of sizes (a captured graph has fixed sizes: the warm call leaves it here)"""
-    key = (device, tuple(sizes))
-    t = _offsets_cache.get(key)
-    if t is None:
-        if len(_offsets_cache) >= 64:
-            _offsets_cache.clear()
-        t = _offsets_cache[key] = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).to(device)
-    return t
-
-
 class TTAViews(list):
     """The 4 B clouds as a list of [N_i, C] tensors (what Voxelizer.generate_padded takes), views of `packed` [4 N, C]; `offsets` is
     the int32 [4 B + 1] device array the kernel wrote."""
@@ -66,7 +55,7 @@ def tta_views(points: Union[torch.Tensor, Sequence[torch.Tensor]], tt_rotation: 
         assert isinstance(points, torch.Tensor) and sum(sizes) == points.shape[0], "sizes name the rows of one packed tensor"
     pts = (clouds[0] if len(clouds) == 1 else torch.cat(clouds)).contiguous().float()
     device, n, ndim, batch = pts.device, int(pts.shape[0]), int(pts.shape[1]), len(sizes)
-    offs = _device_offsets(device, sizes)
+    offs = L.point_offsets(_offsets_cache, device, sizes)
     out = torch.empty((4 * n, ndim), dtype=torch.float32, device=device)
     out_offs = torch.empty((4 * batch + 1,), dtype=torch.int32, device=device)
     cs, sn = _cos_sin(tt_rotation) if tt_rotation != 0 else (1.0, 0.0)

@@ -38,10 +38,6 @@ def _gpu(what, *tensors):
             raise L.LinkAmdError(f"{what}: link_amd runs on the GPU only (got a CPU tensor or an array); there is no CPU fallback")
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _trig(a):
     """cos / sin of a float32 tensor, correctly rounded (through float64), as the kernels form them"""
     d = a.double()
@@ -138,7 +134,7 @@ class BEVFeatureExtractor(nn.Module):
         strides = (ctypes.c_int64 * 4)(*[bev.stride(d) if bev.shape[d] > 1 else 0 for d in range(4)])
         with torch.cuda.device(bev.device):
             L.check(L.lib().link_roi_bev_features(bev.data_ptr(), _IO[bev.dtype], strides, B, C, H, W, boxes.data_ptr(), R, box_len, rot_col,
-                                                  _ptr(labels), _ptr(sel), S, int(num_point), (ctypes.c_float * 2)(*self.pc_start),
+                                                  L.ptr(labels), L.ptr(sel), S, int(num_point), (ctypes.c_float * 2)(*self.pc_start),
                                                   (ctypes.c_float * 2)(*self.voxel_size), self.out_stride, out.data_ptr(),
                                                   L.current_stream_handle()), "link_roi_bev_features")
         return out
@@ -212,7 +208,7 @@ class ProposalTargetLayer(nn.Module):
                "status": torch.empty(B, dtype=torch.int32, device=dev)}
         with torch.cuda.device(dev):
             L.check(L.lib().link_roi_assign(
-                rois_f.data_ptr(), labels_l.data_ptr(), scores_f.data_ptr(), gt_f.data_ptr() if G else None, _ptr(noise), _ptr(sampled_inds),
+                rois_f.data_ptr(), labels_l.data_ptr(), scores_f.data_ptr(), gt_f.data_ptr() if G else None, L.ptr(noise), L.ptr(sampled_inds),
                 B, R, G, M, code, float(_get(cfg, "FG_RATIO")), int(bool(_get(cfg, "SAMPLE_ROI_BY_EACH_CLASS", False))),
                 int(_get(cfg, "CLS_SCORE_TYPE") == "roi_iou"), float(_get(cfg, "CLS_FG_THRESH")), float(_get(cfg, "CLS_BG_THRESH")),
                 float(_get(cfg, "CLS_BG_THRESH_LO")), float(_get(cfg, "HARD_BG_RATIO")), float(_get(cfg, "REG_FG_THRESH")),

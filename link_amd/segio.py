@@ -161,17 +161,6 @@ class _Quantizer:
         self._ws = _Workspace()
         self._offsets = {}
 
-    def _point_offsets(self, device, sizes):
-        """int32 [B + 1] on the device; kept per tuple of sizes, so a call with sizes seen before copies nothing from the host (a
-        captured graph has fixed sizes: the call that warms it up leaves the tensor here)"""
-        key = (device, tuple(sizes))
-        t = self._offsets.get(key)
-        if t is None:
-            if len(self._offsets) >= 64:
-                self._offsets.clear()
-            t = self._offsets[key] = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).to(device)
-        return t
-
     def run(self, clouds: Sequence[torch.Tensor], mode: int, voxel_size: float = 1.0, capacity: Optional[int] = None):
         """-> (coords int32 [cap, 4] = x, y, z, b, indices int32 [cap], inverse int32 [n], inverse_local int32 [n],
         voxel_offsets int32 [B + 1], status int32 [4]), all on the clouds' device"""
@@ -203,7 +192,7 @@ class _Quantizer:
         if mode == L.SEGQ_ROUND and ndim > 16:
             pts, ndim = pts[:, :3].contiguous(), 3
         ws = self._ws.get(device, n, len(clouds))
-        offs = self._point_offsets(device, sizes)
+        offs = L.point_offsets(self._offsets, device, sizes)
         coords = torch.empty((cap, 4), dtype=torch.int32, device=device)
         indices = torch.empty((cap,), dtype=torch.int32, device=device)
         inverse = torch.empty((2, n), dtype=torch.int32, device=device)

@@ -52,17 +52,6 @@ class _Engine:
         self._ws = {}
         self._offsets = {}
 
-    def _point_offsets(self, device, sizes):
-        """int32 [B + 1] on the device; kept per tuple of sizes, so a call with sizes seen before copies nothing from the host (a
-        captured graph has fixed sizes: the call that warms it up leaves the tensor here)"""
-        key = (device, tuple(sizes))
-        t = self._offsets.get(key)
-        if t is None:
-            if len(self._offsets) >= 64:
-                self._offsets.clear()
-            t = self._offsets[key] = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).to(device)
-        return t
-
     def _workspace(self, g: L.LinkVoxelizeGeom, device, batch: int, ncap: int):
         cells = 1
         for d in range(3):
@@ -103,7 +92,7 @@ class _Engine:
         if voxel_capacity is None:
             voxel_capacity = min(n, batch * max_voxels) if self.mode == L.VOXELIZE_HARD else n
         cap = int(voxel_capacity)
-        offs = self._point_offsets(device, sizes)
+        offs = L.point_offsets(self._offsets, device, sizes)
         mean = torch.empty((cap, ndim), dtype=torch.float32, device=device)
         coors = torch.empty((cap, 4), dtype=torch.int32, device=device)
         num = torch.empty((cap,), dtype=torch.int32, device=device)
