@@ -22,6 +22,24 @@ inline int check_launch(const char *what) {
 
 inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
 
+// Launch of a kernel with `lds` bytes of dynamic LDS.  Above the default limit of 64 KiB the kernel has to opt in
+// (hipFuncAttributeMaxDynamicSharedMemorySize; 160 KiB per CU on gfx950).  That is done on every call: it is per device and
+// cheap (a host-side table write), and a process-wide once-flag is one a second GPU or a device reset would never pass again.
+// launch_kernel_unchecked is for launchers that check once after several launches.
+template <class... P, class... A>
+__forceinline__ void launch_kernel_unchecked(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A &&...args) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+}
+
+template <class... P, class... A>
+__forceinline__ int launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const char *what,
+                           A &&...args) {
+  launch_kernel_unchecked(kernel, grid, block, lds, st, static_cast<A &&>(args)...);
+  return check_launch(what);
+}
+
 inline unsigned blocks_for(int64_t n, int threads) {
   int64_t b = (n + threads - 1) / threads;
   return (unsigned)(b < 1 ? 1 : b);

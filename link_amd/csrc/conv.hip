@@ -17,6 +17,7 @@
 //
 // out[v, co] = sum_k sum_ci feats[nbr[v, k], ci] * w[k, ci, co]          (nbr < 0: absent)
 #include "common.h"
+#include "dispatch.h"
 
 using namespace link;
 
@@ -559,20 +560,12 @@ static int launch_conv_resident(const float *feats, const int32_t *nbr, const fl
   const int per_cu = (160 * 1024) / K::LDS_BYTES;
   int64_t wgs = (tiles + K::NW - 1) / K::NW;
   if (wgs > 256 * per_cu) wgs = 256 * per_cu;
-  if (split) {
-    if (K::LDS_BYTES > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_resident<CI, CO, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-    hipLaunchKernelGGL((k_subm_conv_resident<CI, CO, true>), dim3((unsigned)wgs), dim3(64 * K::NW), K::LDS_BYTES, st, feats, nbr, w,
-                       order, n, kvol, out, ep);
-  } else {
-    if (K::LDS_BYTES > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_resident<CI, CO, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-    hipLaunchKernelGGL((k_subm_conv_resident<CI, CO, false>), dim3((unsigned)wgs), dim3(64 * K::NW), K::LDS_BYTES, st, feats, nbr, w,
-                       order, n, kvol, out, ep);
-  }
-  return check_launch("link_subm_conv_forward");
+  int rc = LINK_ERR_ARG;
+  dispatch_bool(split, [&](auto sp) {
+    rc = launch_kernel(k_subm_conv_resident<CI, CO, decltype(sp)::value>, dim3((unsigned)wgs), dim3(64 * K::NW), K::LDS_BYTES, st,
+                       "link_subm_conv_forward", feats, nbr, w, order, n, kvol, out, ep);
+  });
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -754,16 +747,12 @@ static int launch_conv_resident_amp(const void *feats, int io, const int32_t *nb
   if (wgs > 256 * per_cu) wgs = 256 * per_cu;
   const unsigned short *f = static_cast<const unsigned short *>(feats), *w16 = static_cast<const unsigned short *>(wt);
   unsigned short *o = static_cast<unsigned short *>(out);
-  if (io == LINK_IO_BF16) {
-    if (K::LDS_BYTES > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_resident_amp<CI, CO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-    hipLaunchKernelGGL((k_subm_conv_resident_amp<CI, CO, true>), dim3((unsigned)wgs), dim3(512), K::LDS_BYTES, st, f, nbr, w16, order, n, kvol, o, ep);
-  } else {
-    if (K::LDS_BYTES > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_resident_amp<CI, CO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-    hipLaunchKernelGGL((k_subm_conv_resident_amp<CI, CO, false>), dim3((unsigned)wgs), dim3(512), K::LDS_BYTES, st, f, nbr, w16, order, n, kvol, o, ep);
-  }
-  return check_launch("link_subm_conv_resident_amp");
+  int rc = LINK_ERR_ARG;
+  dispatch_bool(io == LINK_IO_BF16, [&](auto bf) {
+    rc = launch_kernel(k_subm_conv_resident_amp<CI, CO, decltype(bf)::value>, dim3((unsigned)wgs), dim3(512), K::LDS_BYTES, st,
+                       "link_subm_conv_resident_amp", f, nbr, w16, order, n, kvol, o, ep);
+  });
+  return rc;
 }
 
 extern "C" int link_subm_conv_resident_amp(const void *feats, int32_t io_dtype, const int32_t *nbr, const void *wt,
@@ -775,12 +764,11 @@ extern "C" int link_subm_conv_resident_amp(const void *feats, int32_t io_dtype, 
   if (n == 0) return LINK_OK;
   if (!feats || !nbr || !wt || !out) return LINK_ERR_ARG;
   const conv_epilogue_amp ep = {ln_w, ln_b, static_cast<const unsigned short *>(addend), eps, relu & 3};
-  hipStream_t st = S(stream);
-  if (cin == 16 && cout == 16) return launch_conv_resident_amp<16, 16>(feats, io_dtype, nbr, wt, order, n, kvol, out, ep, st);
-  if (cin == 32 && cout == 32) return launch_conv_resident_amp<32, 32>(feats, io_dtype, nbr, wt, order, n, kvol, out, ep, st);
-  if (cin == 16 && cout == 32) return launch_conv_resident_amp<16, 32>(feats, io_dtype, nbr, wt, order, n, kvol, out, ep, st);
-  if (cin == 32 && cout == 16) return launch_conv_resident_amp<32, 16>(feats, io_dtype, nbr, wt, order, n, kvol, out, ep, st);
-  return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_resident(cin, cout, [&](auto ci, auto co) {
+    rc = launch_conv_resident_amp<decltype(ci)::value, decltype(co)::value>(feats, io_dtype, nbr, wt, order, n, kvol, out, ep, S(stream));
+  });
+  return rc;
 }
 
 // any Cin / Cout <= 256: one wave per output voxel, lanes = output channels (no MFMA; small widths)
@@ -958,29 +946,27 @@ __global__ void __launch_bounds__(256, 4) k_subm_conv_wgrad(const float *__restr
 
 extern "C" int32_t link_subm_conv_wgrad_chunks(void) { return 16; }
 
-extern "C" int link_subm_conv_wgrad(const float *feats, const float *gout, const int32_t *nbr_t, int64_t n,
-                                    int32_t c, int32_t kvol, float *partial, void *stream) {
-  if (n < 0 || c <= 0 || c > 64 || (c & 3) != 0 || kvol <= 0) return LINK_ERR_ARG;
-  if (!partial) return LINK_ERR_ARG;
-  if (n > 0 && (!feats || !gout || !nbr_t)) return LINK_ERR_ARG;
-  const int chunks = link_subm_conv_wgrad_chunks();
-  hipLaunchKernelGGL(k_subm_conv_wgrad, dim3((unsigned)(kvol * chunks)), dim3(256), 0, S(stream), feats, gout, nbr_t, n,
-                     (int)c, (int)kvol, chunks, 0, partial);
-  return check_launch("link_subm_conv_wgrad");
-}
-
 // Round 5: the caller picks the split.  partial = f32[(kvol * chunks + centre_extra)][c][c]; g_w[k] = sum over chunk of slot
 // [chunk * kvol + k], plus, for k = kvol / 2, the slots [kvol * chunks, kvol * chunks + centre_extra).  centre_extra > 0 only
 // for tables whose centre column is dense (odd kernel over one coordinate set).
-extern "C" int link_subm_conv_wgrad_split(const float *feats, const float *gout, const int32_t *nbr_t, int64_t n, int32_t c,
-                                          int32_t kvol, int32_t chunks, int32_t centre_extra, float *partial, void *stream) {
+static int subm_conv_wgrad(const float *feats, const float *gout, const int32_t *nbr_t, int64_t n, int32_t c, int32_t kvol,
+                           int32_t chunks, int32_t centre_extra, float *partial, void *stream, const char *what) {
   if (n < 0 || c <= 0 || c > 64 || (c & 3) != 0 || kvol <= 0 || chunks < 1 || chunks > 1024 || centre_extra < 0 || centre_extra > 4096)
     return LINK_ERR_ARG;
   if (!partial) return LINK_ERR_ARG;
   if (n > 0 && (!feats || !gout || !nbr_t)) return LINK_ERR_ARG;
-  hipLaunchKernelGGL(k_subm_conv_wgrad, dim3((unsigned)(kvol * chunks + centre_extra)), dim3(256), 0, S(stream), feats, gout, nbr_t, n,
-                     (int)c, (int)kvol, (int)chunks, (int)centre_extra, partial);
-  return check_launch("link_subm_conv_wgrad_split");
+  return launch_kernel(k_subm_conv_wgrad, dim3((unsigned)(kvol * chunks + centre_extra)), dim3(256), 0, S(stream), what, feats, gout, nbr_t, n,
+                       (int)c, (int)kvol, (int)chunks, (int)centre_extra, partial);
+}
+
+extern "C" int link_subm_conv_wgrad(const float *feats, const float *gout, const int32_t *nbr_t, int64_t n,
+                                    int32_t c, int32_t kvol, float *partial, void *stream) {
+  return subm_conv_wgrad(feats, gout, nbr_t, n, c, kvol, link_subm_conv_wgrad_chunks(), 0, partial, stream, "link_subm_conv_wgrad");
+}
+
+extern "C" int link_subm_conv_wgrad_split(const float *feats, const float *gout, const int32_t *nbr_t, int64_t n, int32_t c,
+                                          int32_t kvol, int32_t chunks, int32_t centre_extra, float *partial, void *stream) {
+  return subm_conv_wgrad(feats, gout, nbr_t, n, c, kvol, chunks, centre_extra, partial, stream, "link_subm_conv_wgrad_split");
 }
 
 // g_w from the partial slots of link_subm_conv_wgrad_split in ONE launch (round 6): g_w[k] = sum over chunk of slot [chunk * kvol + k]
@@ -1038,24 +1024,15 @@ template <int CI, int CO, int NT>
 static int launch_conv_mfma_nt(const float *feats, const int32_t *nbr, const float *w, const int32_t *order,
                                int64_t n, int kvol, float *out, const conv_epilogue &ep, hipStream_t st) {
   const size_t lds = ((size_t)2 * CO * (CI + 4) + (size_t)4 * 27 * NT * 16) * sizeof(float);
-  if (lds > 64 * 1024) {
-    // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
-    // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_mfma<CI, CO, NT, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   const int64_t tiles = (n + 15) / 16;
   int64_t wgs = (tiles + 4 * NT - 1) / (4 * NT);
   if (wgs > g_conv_wgs) wgs = g_conv_wgs;
   if (NT == 1 && g_conv_deep && tiles <= 1024) {      // <= 16k voxels: a wave or two per SIMD, the latency-bound regime (larger frames lose occupancy to the extra register sets)
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_subm_conv_mfma<CI, CO, 1, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_subm_conv_mfma<CI, CO, 1, true>), dim3((unsigned)wgs), dim3(256), lds, st, feats, nbr, w, order, n, kvol, out, ep);
-    return check_launch("link_subm_conv_forward");
+    return launch_kernel(k_subm_conv_mfma<CI, CO, 1, true>, dim3((unsigned)wgs), dim3(256), lds, st, "link_subm_conv_forward", feats, nbr, w,
+                         order, n, kvol, out, ep);
   }
-  hipLaunchKernelGGL((k_subm_conv_mfma<CI, CO, NT, false>), dim3((unsigned)wgs), dim3(256), lds, st, feats, nbr, w, order, n, kvol, out, ep);
-  return check_launch("link_subm_conv_forward");
+  return launch_kernel(k_subm_conv_mfma<CI, CO, NT, false>, dim3((unsigned)wgs), dim3(256), lds, st, "link_subm_conv_forward", feats, nbr, w,
+                       order, n, kvol, out, ep);
 }
 
 // tiles per wave: as few as still fills the chip (more workgroups = more latency hiding; fewer = less
@@ -1075,7 +1052,34 @@ static int launch_conv_mfma(const float *feats, const int32_t *nbr, const float 
 
 static int subm_conv_impl(const float *feats, const int32_t *nbr, const float *w, const int32_t *order,
                           int64_t n, int32_t cin, int32_t cout, int32_t kvol, float *out,
-                          const conv_epilogue &ep, void *stream);
+                          const conv_epilogue &ep, void *stream) {
+  if (n < 0 || cin <= 0 || cout <= 0 || cin > 256 || cout > 256 || kvol <= 0) return LINK_ERR_ARG;
+  const bool mfma_ok = (cin & 15) == 0 && (cout & 15) == 0 && cin <= 128 && cout <= 128 && kvol <= 27;
+  if (n == 0) return LINK_OK;
+  if (!feats || !nbr || !w || !out) return LINK_ERR_ARG;
+  hipStream_t st = S(stream);
+  int rc = LINK_ERR_ARG;
+  if (mfma_ok && kvol <= 27 && n >= CONV_RESIDENT_MIN) {          // narrow layers: every W_k resident in LDS
+    // the fused inference forms (epilogue set: link_subm_conv_ln_add_relu) take the fp16-split products, like the pair-list
+    // form's inference kernel; the plain forward (what autograd records) stays on the exact f32 instruction
+    const bool split = ep.ln_w != nullptr;
+    const bool resident = dispatch_conv_resident(cin, cout, [&](auto ci, auto co) {
+      rc = launch_conv_resident<decltype(ci)::value, decltype(co)::value>(feats, nbr, w, order, n, kvol, out, ep, split, st);
+    });
+    if (resident) return rc;
+  }
+  if (mfma_ok) {
+    const bool table = dispatch_conv_table(cin, cout, [&](auto ci, auto co) {
+      rc = launch_conv_mfma<decltype(ci)::value, decltype(co)::value>(feats, nbr, w, order, n, kvol, out, ep, st);
+    });
+    if (table) return rc;
+  }
+  dispatch_cpl(cout, [&](auto cpl) {                   // any other width: lane = channel
+    rc = launch_kernel(k_subm_conv_generic<decltype(cpl)::value>, dim3(blocks_for(n * 64, 256)), dim3(256), 0, st, "link_subm_conv_forward", feats,
+                       nbr, w, n, (int)cin, (int)cout, (int)kvol, out, ep);
+  });
+  return rc;
+}
 
 extern "C" int link_subm_conv_forward(const float *feats, const int32_t *nbr, const float *w,
                                       const int32_t *order, int64_t n, int32_t cin, int32_t cout,
@@ -1091,40 +1095,4 @@ extern "C" int link_subm_conv_ln_add_relu(const float *feats, const int32_t *nbr
   if (!ln_w || !ln_b) return LINK_ERR_ARG;
   const conv_epilogue ep = {ln_w, ln_b, addend, eps, relu & 3};
   return subm_conv_impl(feats, nbr, w, order, n, cin, cout, kvol, out, ep, stream);
-}
-
-static int subm_conv_impl(const float *feats, const int32_t *nbr, const float *w, const int32_t *order,
-                          int64_t n, int32_t cin, int32_t cout, int32_t kvol, float *out,
-                          const conv_epilogue &ep, void *stream) {
-  if (n < 0 || cin <= 0 || cout <= 0 || cin > 256 || cout > 256 || kvol <= 0) return LINK_ERR_ARG;
-  const bool mfma_ok = (cin & 15) == 0 && (cout & 15) == 0 && cin <= 128 && cout <= 128 && kvol <= 27;
-  if (n == 0) return LINK_OK;
-  if (!feats || !nbr || !w || !out) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  if (mfma_ok && kvol <= 27 && n >= CONV_RESIDENT_MIN) {          // narrow layers: every W_k resident in LDS
-    // the fused inference forms (epilogue set: link_subm_conv_ln_add_relu) take the fp16-split products, like the pair-list
-    // form's inference kernel; the plain forward (what autograd records) stays on the exact f32 instruction
-    const bool split = ep.ln_w != nullptr;
-    if (cin == 16 && cout == 16) return launch_conv_resident<16, 16>(feats, nbr, w, order, n, kvol, out, ep, split, st);
-    if (cin == 32 && cout == 32) return launch_conv_resident<32, 32>(feats, nbr, w, order, n, kvol, out, ep, split, st);
-    if (cin == 16 && cout == 32) return launch_conv_resident<16, 32>(feats, nbr, w, order, n, kvol, out, ep, split, st);
-    if (cin == 32 && cout == 16) return launch_conv_resident<32, 16>(feats, nbr, w, order, n, kvol, out, ep, split, st);
-  }
-  if (mfma_ok) {
-#define LINK_CONV(I, O) if (cin == I && cout == O) return launch_conv_mfma<I, O>(feats, nbr, w, order, n, kvol, out, ep, st)
-    LINK_CONV(16, 16); LINK_CONV(32, 32); LINK_CONV(48, 48); LINK_CONV(64, 64); LINK_CONV(80, 80); LINK_CONV(96, 96);
-    LINK_CONV(112, 112); LINK_CONV(128, 128);
-    // the channel changes of the reference encoders (cs = [32,32,64,128,256,256,128,96,96] x cr, linkunet.py:262)
-    LINK_CONV(16, 32); LINK_CONV(32, 16); LINK_CONV(32, 64); LINK_CONV(64, 32); LINK_CONV(64, 128); LINK_CONV(128, 64);
-    LINK_CONV(96, 128); LINK_CONV(128, 96); LINK_CONV(64, 96); LINK_CONV(96, 64); LINK_CONV(32, 96); LINK_CONV(96, 32);
-    LINK_CONV(16, 64); LINK_CONV(64, 16); LINK_CONV(32, 128); LINK_CONV(128, 32);
-#undef LINK_CONV
-  }
-  dim3 grid(blocks_for(n * 64, 256)), block(256);
-  const int cpl = (cout + 63) / 64;
-  if (cpl == 1) hipLaunchKernelGGL(k_subm_conv_generic<1>, grid, block, 0, st, feats, nbr, w, n, (int)cin, (int)cout, (int)kvol, out, ep);
-  else if (cpl == 2) hipLaunchKernelGGL(k_subm_conv_generic<2>, grid, block, 0, st, feats, nbr, w, n, (int)cin, (int)cout, (int)kvol, out, ep);
-  else if (cpl == 3) hipLaunchKernelGGL(k_subm_conv_generic<3>, grid, block, 0, st, feats, nbr, w, n, (int)cin, (int)cout, (int)kvol, out, ep);
-  else hipLaunchKernelGGL(k_subm_conv_generic<4>, grid, block, 0, st, feats, nbr, w, n, (int)cin, (int)cout, (int)kvol, out, ep);
-  return check_launch("link_subm_conv_forward");
 }

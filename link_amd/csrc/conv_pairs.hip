@@ -21,6 +21,7 @@
 // The pair lists are the kernel map (the reference's nbmaps/nbsizes, nn/functional/conv.py:109-122): built once
 // per coordinate set on the host side (link_amd/elk.py::_pair_plan) and cached with it.
 #include "common.h"
+#include "dispatch.h"
 
 using namespace link;
 
@@ -495,57 +496,40 @@ __global__ void __launch_bounds__(256) k_conv_pairs_sum(const float *__restrict_
   }
 }
 
-template <int CI, int CO>
-static int launch_pairs_gemm(const void *feats, int io, const int32_t *pair_in, const int32_t *wg_k, int64_t granules,
-                             const float *w, float *contrib, hipStream_t st) {
-  const size_t lds = (size_t)CI * (CO + 4) * sizeof(float);
-  if (lds > 64 * 1024)      // per device and cheap: no process-wide "done" flag
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_pairs_gemm<CI, CO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_conv_pairs_gemm<CI, CO>), dim3((unsigned)granules), dim3(512), lds, st, feats, io, pair_in, wg_k, w, contrib);
-  return check_launch("link_conv_pairs_gemm");
+// ---- host side: the width pairs are dispatch_conv_pairs' list (dispatch.h), nowhere else ----
+extern "C" int link_conv_pairs_supported(int32_t cin, int32_t cout) {
+  return dispatch_conv_pairs(cin, cout, [](auto, auto) {}) ? 1 : 0;
 }
 
-extern "C" int link_conv_pairs_supported(int32_t cin, int32_t cout) {
-  const bool sq = cin == cout && (cin == 16 || cin == 32 || cin == 64 || cin == 128);
-  const bool rect = (cin == 16 && cout == 32) || (cin == 32 && cout == 16) || (cin == 32 && cout == 64) ||
-                    (cin == 64 && cout == 32) || (cin == 64 && cout == 128) || (cin == 128 && cout == 64) ||
-                    (cin == 16 && cout == 64) || (cin == 64 && cout == 16);
-  return (sq || rect) ? 1 : 0;
+// Argument checks the entry points share.  Their order is part of the ABI: the row type first, then these -- an unsupported
+// width is refused even when there is nothing to do -- then LINK_OK for nothing to do, and only then the null pointers.
+static bool pairs_rows_ok(int64_t rows_pad, int cin, int cout) {      // whole 128-row granules, 32-bit row numbers
+  return rows_pad >= 0 && !(rows_pad & 127) && rows_pad < (1LL << 31) && link_conv_pairs_supported(cin, cout);
+}
+static bool centre_sum_ok(int64_t n, int centre, int cin, int cout, const float *ln_w, const float *ln_b, int64_t contrib_rows) {
+  if (n < 0 || centre < 0 || !link_conv_pairs_supported(cin, cout) || (ln_w == nullptr) != (ln_b == nullptr)) return false;
+  return contrib_rows >= 0 && contrib_rows * (int64_t)cout * 4 < 0xFFFFFFF0LL;   // 32-bit row offsets
 }
 
 extern "C" int link_conv_pairs_gemm_io(const void *feats, int32_t io_dtype, const int32_t *pair_in, const int32_t *wg_k,
-                                       int64_t rows_pad, const float *w, int32_t cin, int32_t cout, float *contrib, void *stream);
+                                       int64_t rows_pad, const float *w, int32_t cin, int32_t cout, float *contrib, void *stream) {
+  if (io_dtype < 0 || io_dtype > 2) return LINK_ERR_ARG;
+  if (!pairs_rows_ok(rows_pad, cin, cout)) return LINK_ERR_ARG;
+  if (rows_pad == 0) return LINK_OK;
+  if (!feats || !pair_in || !wg_k || !w || !contrib) return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+    constexpr int CI = decltype(ci)::value, CO = decltype(co)::value;
+    rc = launch_kernel(k_conv_pairs_gemm<CI, CO>, dim3((unsigned)(rows_pad / 128)), dim3(512), (size_t)CI * (CO + 4) * sizeof(float), S(stream),
+                       "link_conv_pairs_gemm", feats, (int)io_dtype, pair_in, wg_k, w, contrib);
+  });
+  return rc;
+}
 extern "C" int link_conv_pairs_gemm(const float *feats, const int32_t *pair_in, const int32_t *wg_k, int64_t rows_pad,
                                     const float *w, int32_t cin, int32_t cout, float *contrib, void *stream) {
   return link_conv_pairs_gemm_io(feats, LINK_IO_F32, pair_in, wg_k, rows_pad, w, cin, cout, contrib, stream);
 }
-extern "C" int link_conv_pairs_gemm_io(const void *feats, int32_t io_dtype, const int32_t *pair_in, const int32_t *wg_k,
-                                       int64_t rows_pad, const float *w, int32_t cin, int32_t cout, float *contrib, void *stream) {
-  if (io_dtype < 0 || io_dtype > 2) return LINK_ERR_ARG;
-  if (rows_pad < 0 || (rows_pad & 127) || rows_pad >= (1LL << 31) || !link_conv_pairs_supported(cin, cout)) return LINK_ERR_ARG;
-  if (rows_pad == 0) return LINK_OK;
-  if (!feats || !pair_in || !wg_k || !w || !contrib) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  const int64_t gr = rows_pad / 128;
-#define LINK_CP(I, O) if (cin == I && cout == O) return launch_pairs_gemm<I, O>(feats, (int)io_dtype, pair_in, wg_k, gr, w, contrib, st)
-  LINK_CP(16, 16); LINK_CP(32, 32); LINK_CP(64, 64); LINK_CP(128, 128);
-  LINK_CP(16, 32); LINK_CP(32, 16); LINK_CP(32, 64); LINK_CP(64, 32); LINK_CP(64, 128); LINK_CP(128, 64);
-  LINK_CP(16, 64); LINK_CP(64, 16);
-#undef LINK_CP
-  return LINK_ERR_ARG;
-}
 
-extern "C" int link_conv_pairs_sum_io(const float *contrib, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
-                                      int64_t n_direct, int32_t cout, const float *bias, const float *ln_w, const float *ln_b,
-                                      float eps, const void *addend, int32_t relu, void *out, int32_t io_dtype, void *stream);
-extern "C" int link_conv_pairs_sum(const float *contrib, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
-                                   int64_t n_direct, int32_t cout, const float *bias, const float *ln_w,
-                                   const float *ln_b, float eps, const float *addend, int32_t relu, float *out,
-                                   void *stream) {
-  return link_conv_pairs_sum_io(contrib, ext_start, ext_list, n, n_direct, cout, bias, ln_w, ln_b, eps, addend, relu, out,
-                                LINK_IO_F32, stream);
-}
 extern "C" int link_conv_pairs_sum_io(const float *contrib, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
                                       int64_t n_direct, int32_t cout, const float *bias, const float *ln_w, const float *ln_b,
                                       float eps, const void *addend, int32_t relu, void *out, int32_t io_dtype, void *stream) {
@@ -555,24 +539,28 @@ extern "C" int link_conv_pairs_sum_io(const float *contrib, const int32_t *ext_s
   if ((ln_w == nullptr) != (ln_b == nullptr)) return LINK_ERR_ARG;
   if (n == 0) return LINK_OK;
   if (!contrib || !ext_start || !ext_list || !out) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  const bool tail = ln_w != nullptr;
-  const int lpr = cout / 4, gpw = 64 / lpr;
+  const int gpw = 64 / (cout / 4);
   int64_t wgs = (n + 4 * gpw - 1) / (4 * gpw);
   if (wgs > 4096) wgs = 4096;
-#define LINK_CS(LPRV)                                                                                                  \
-  if (lpr == LPRV) {                                                                                                   \
-    if (tail) hipLaunchKernelGGL((k_conv_pairs_sum<LPRV, true>), dim3((unsigned)wgs), dim3(256), 0, st, contrib, ext_start,  \
-                                 ext_list, n, n_direct, bias, ln_w, ln_b, eps, addend, (int)relu, out, (int)io_dtype); \
-    else hipLaunchKernelGGL((k_conv_pairs_sum<LPRV, false>), dim3((unsigned)wgs), dim3(256), 0, st, contrib, ext_start,      \
-                            ext_list, n, n_direct, bias, ln_w, ln_b, eps, addend, (int)relu, out, (int)io_dtype);      \
-    return check_launch("link_conv_pairs_sum");                                                                        \
-  }
-  LINK_CS(4) LINK_CS(8) LINK_CS(16) LINK_CS(32)
-#undef LINK_CS
-  return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_int<4, 8, 16, 32>(cout / 4, [&](auto lpr) {
+    return dispatch_bool(ln_w != nullptr, [&](auto tail) {
+      rc = launch_kernel(k_conv_pairs_sum<decltype(lpr)::value, decltype(tail)::value>, dim3((unsigned)wgs), dim3(256), 0, S(stream),
+                         "link_conv_pairs_sum", contrib, ext_start, ext_list, n, n_direct, bias, ln_w, ln_b, eps, addend, (int)relu, out,
+                         (int)io_dtype);
+    });
+  });
+  return rc;
+}
+extern "C" int link_conv_pairs_sum(const float *contrib, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
+                                   int64_t n_direct, int32_t cout, const float *bias, const float *ln_w,
+                                   const float *ln_b, float eps, const float *addend, int32_t relu, float *out,
+                                   void *stream) {
+  return link_conv_pairs_sum_io(contrib, ext_start, ext_list, n, n_direct, cout, bias, ln_w, ln_b, eps, addend, relu, out,
+                                LINK_IO_F32, stream);
 }
 
+// MM as in k_conv_centre_sum; the TAIL kernel when a LayerNorm / affine follows
 template <int CI, int CO, int MM>
 static int launch_centre_sum(const void *feats, int io, const void *w, int centre, const void *contrib, uint32_t cbytes, const int32_t *ext_start,
                              const int32_t *ext_list, int64_t n, const float *bias, const float *ln_w, const float *ln_b,
@@ -586,26 +574,30 @@ static int launch_centre_sum(const void *feats, int io, const void *w, int centr
 #endif
   const unsigned nt = n > CP_NT_BIG ? 512u : (n > CP_NT_MID ? 256u : 128u);
   const unsigned wgs = (unsigned)((n + nt / 4 - 1) / (nt / 4));
-  if (ln_w) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_centre_sum<CI, CO, true, MM>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_conv_centre_sum<CI, CO, true, MM>), dim3(wgs), dim3(nt), lds, st, feats, io, w, centre, contrib, cbytes, ext_start,
-                       ext_list, n, bias, ln_w, ln_b, eps, addend, relu, out);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_centre_sum<CI, CO, false, MM>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_conv_centre_sum<CI, CO, false, MM>), dim3(wgs), dim3(nt), lds, st, feats, io, w, centre, contrib, cbytes, ext_start,
-                       ext_list, n, bias, ln_w, ln_b, eps, addend, relu, out);
-  }
-  return check_launch("link_conv_centre_sum");
+  int rc = LINK_ERR_ARG;
+  dispatch_bool(ln_w != nullptr, [&](auto tail) {
+    rc = launch_kernel(k_conv_centre_sum<CI, CO, decltype(tail)::value, MM>, dim3(wgs), dim3(nt), lds, st, "link_conv_centre_sum", feats, io, w,
+                       centre, contrib, cbytes, ext_start, ext_list, n, bias, ln_w, ln_b, eps, addend, relu, out);
+  });
+  return rc;
 }
 
 extern "C" int link_conv_centre_sum_io(const void *feats, const float *w, int32_t centre, const float *contrib,
                                        int64_t contrib_rows, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
                                        int32_t cin, int32_t cout, const float *bias, const float *ln_w, const float *ln_b, float eps,
-                                       const void *addend, int32_t relu, void *out, int32_t io_dtype, void *stream);
+                                       const void *addend, int32_t relu, void *out, int32_t io_dtype, void *stream) {
+  if (io_dtype < 0 || io_dtype > 2) return LINK_ERR_ARG;
+  if (!centre_sum_ok(n, centre, cin, cout, ln_w, ln_b, contrib_rows)) return LINK_ERR_ARG;
+  const uint32_t cbytes = (uint32_t)(contrib_rows * cout * 4);
+  if (n == 0) return LINK_OK;
+  if (!feats || !w || !ext_start || !out || (contrib_rows > 0 && (!contrib || !ext_list))) return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+    rc = launch_centre_sum<decltype(ci)::value, decltype(co)::value, 0>(feats, (int)io_dtype, w, centre, contrib, cbytes, ext_start, ext_list,
+                                                                        n, bias, ln_w, ln_b, eps, addend, (int)relu, out, S(stream));
+  });
+  return rc;
+}
 extern "C" int link_conv_centre_sum(const float *feats, const float *w, int32_t centre, const float *contrib,
                                     int64_t contrib_rows, const int32_t *ext_start, const int32_t *ext_list, int64_t n, int32_t cin,
                                     int32_t cout, const float *bias, const float *ln_w, const float *ln_b, float eps,
@@ -613,86 +605,41 @@ extern "C" int link_conv_centre_sum(const float *feats, const float *w, int32_t 
   return link_conv_centre_sum_io(feats, w, centre, contrib, contrib_rows, ext_start, ext_list, n, cin, cout, bias, ln_w, ln_b, eps,
                                  addend, relu, out, LINK_IO_F32, stream);
 }
-extern "C" int link_conv_centre_sum_io(const void *feats, const float *w, int32_t centre, const float *contrib,
-                                       int64_t contrib_rows, const int32_t *ext_start, const int32_t *ext_list, int64_t n,
-                                       int32_t cin, int32_t cout, const float *bias, const float *ln_w, const float *ln_b, float eps,
-                                       const void *addend, int32_t relu, void *out, int32_t io_dtype, void *stream) {
-  if (io_dtype < 0 || io_dtype > 2) return LINK_ERR_ARG;
-  if (n < 0 || centre < 0 || !link_conv_pairs_supported(cin, cout) || (ln_w == nullptr) != (ln_b == nullptr)) return LINK_ERR_ARG;
-  if (contrib_rows < 0 || contrib_rows * (int64_t)cout * 4 >= 0xFFFFFFF0LL) return LINK_ERR_ARG;   // 32-bit row offsets
-  const uint32_t cbytes = (uint32_t)(contrib_rows * cout * 4);
-  if (n == 0) return LINK_OK;
-  if (!feats || !w || !ext_start || !out || (contrib_rows > 0 && (!contrib || !ext_list))) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-#define LINK_CC(I, O) if (cin == I && cout == O) return launch_centre_sum<I, O, 0>(feats, (int)io_dtype, w, centre, contrib, cbytes, ext_start, ext_list, n, bias, ln_w, ln_b, eps, addend, (int)relu, out, st)
-  LINK_CC(16, 16); LINK_CC(32, 32); LINK_CC(64, 64); LINK_CC(128, 128);
-  LINK_CC(16, 32); LINK_CC(32, 16); LINK_CC(32, 64); LINK_CC(64, 32); LINK_CC(64, 128); LINK_CC(128, 64);
-  LINK_CC(16, 64); LINK_CC(64, 16);
-#undef LINK_CC
-  return LINK_ERR_ARG;
-}
-
-template <int CI, int CO>
-static int launch_pairs_gemm_split(const float *feats, const int32_t *pair_in, const int32_t *wg_k, int64_t granules,
-                                   const void *ws, const float *w, const int32_t *w_big, float *contrib, hipStream_t st) {
-  const size_t lds = (size_t)CO * (2 * CI + 8) * 2;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_pairs_gemm_split<CI, CO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_conv_pairs_gemm_split<CI, CO>), dim3((unsigned)granules), dim3(512), lds, st, feats, pair_in, wg_k,
-                     reinterpret_cast<const unsigned short *>(ws), w, w_big, contrib);
-  return check_launch("link_conv_pairs_gemm_split");
-}
 
 extern "C" int link_conv_pairs_gemm_split(const float *feats, const int32_t *pair_in, const int32_t *wg_k, int64_t rows_pad,
                                           const void *ws, const float *w, const int32_t *w_big, int32_t cin, int32_t cout,
                                           float *contrib, void *stream) {
-  if (rows_pad < 0 || (rows_pad & 127) || rows_pad >= (1LL << 31) || !link_conv_pairs_supported(cin, cout)) return LINK_ERR_ARG;
+  if (!pairs_rows_ok(rows_pad, cin, cout)) return LINK_ERR_ARG;
   if (rows_pad == 0) return LINK_OK;
   if (!feats || !pair_in || !wg_k || !ws || !w || !w_big || !contrib) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  const int64_t gr = rows_pad / 128;
-#define LINK_CP(I, O) if (cin == I && cout == O) return launch_pairs_gemm_split<I, O>(feats, pair_in, wg_k, gr, ws, w, w_big, contrib, st)
-  LINK_CP(16, 16); LINK_CP(32, 32); LINK_CP(64, 64); LINK_CP(128, 128);
-  LINK_CP(16, 32); LINK_CP(32, 16); LINK_CP(32, 64); LINK_CP(64, 32); LINK_CP(64, 128); LINK_CP(128, 64);
-  LINK_CP(16, 64); LINK_CP(64, 16);
-#undef LINK_CP
-  return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+    constexpr int CI = decltype(ci)::value, CO = decltype(co)::value;
+    rc = launch_kernel(k_conv_pairs_gemm_split<CI, CO>, dim3((unsigned)(rows_pad / 128)), dim3(512), (size_t)CO * (2 * CI + 8) * 2, S(stream),
+                       "link_conv_pairs_gemm_split", feats, pair_in, wg_k, reinterpret_cast<const unsigned short *>(ws), w, w_big, contrib);
+  });
+  return rc;
 }
 
 // AMP form (see cp_mfma16): 16-bit rows AND 16-bit weights wt[k][cout][cin] of the same type, fp32 accumulation.
-template <int CI, int CO, bool BF, bool C16>
-static int launch_pairs_gemm_h(const void *feats, const int32_t *pair_in, const int32_t *wg_k, int64_t granules,
-                               const void *wt, void *contrib, hipStream_t st) {
-  const size_t lds = (size_t)CO * (CI + 8) * 2;
-  hipLaunchKernelGGL((k_conv_pairs_gemm_h<CI, CO, BF, C16>), dim3((unsigned)granules), dim3(512), lds, st,
-                     reinterpret_cast<const unsigned short *>(feats), pair_in, wg_k, reinterpret_cast<const unsigned short *>(wt), contrib);
-  return check_launch("link_conv_pairs_gemm_amp");
-}
-
 extern "C" int link_conv_pairs_gemm_amp(const void *feats, int32_t io_dtype, const int32_t *pair_in, const int32_t *wg_k,
                                         int64_t rows_pad, const void *wt, int32_t cin, int32_t cout, void *contrib,
                                         int32_t contrib_dtype, void *stream) {
   if (io_dtype != LINK_IO_F16 && io_dtype != LINK_IO_BF16) return LINK_ERR_ARG;
   if (contrib_dtype != LINK_IO_F32 && contrib_dtype != io_dtype) return LINK_ERR_ARG;
-  const bool c16 = contrib_dtype != LINK_IO_F32;
-  if (rows_pad < 0 || (rows_pad & 127) || rows_pad >= (1LL << 31) || !link_conv_pairs_supported(cin, cout)) return LINK_ERR_ARG;
+  if (!pairs_rows_ok(rows_pad, cin, cout)) return LINK_ERR_ARG;
   if (rows_pad == 0) return LINK_OK;
   if (!feats || !pair_in || !wg_k || !wt || !contrib) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-  const int64_t gr = rows_pad / 128;
-#define LINK_CP(I, O)                                                                                                   \
-  if (cin == I && cout == O)                                                                                            \
-    return io_dtype == LINK_IO_BF16                                                                                     \
-               ? (c16 ? launch_pairs_gemm_h<I, O, true, true>(feats, pair_in, wg_k, gr, wt, contrib, st)                \
-                      : launch_pairs_gemm_h<I, O, true, false>(feats, pair_in, wg_k, gr, wt, contrib, st))              \
-               : (c16 ? launch_pairs_gemm_h<I, O, false, true>(feats, pair_in, wg_k, gr, wt, contrib, st)               \
-                      : launch_pairs_gemm_h<I, O, false, false>(feats, pair_in, wg_k, gr, wt, contrib, st))
-  LINK_CP(16, 16); LINK_CP(32, 32); LINK_CP(64, 64); LINK_CP(128, 128);
-  LINK_CP(16, 32); LINK_CP(32, 16); LINK_CP(32, 64); LINK_CP(64, 32); LINK_CP(64, 128); LINK_CP(128, 64);
-  LINK_CP(16, 64); LINK_CP(64, 16);
-#undef LINK_CP
-  return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+    return dispatch_bool2(io_dtype == LINK_IO_BF16, contrib_dtype != LINK_IO_F32, [&](auto bf, auto c16) {
+      constexpr int CI = decltype(ci)::value, CO = decltype(co)::value;
+      rc = launch_kernel(k_conv_pairs_gemm_h<CI, CO, decltype(bf)::value, decltype(c16)::value>, dim3((unsigned)(rows_pad / 128)), dim3(512),
+                         (size_t)CO * (CI + 8) * 2, S(stream), "link_conv_pairs_gemm_amp", reinterpret_cast<const unsigned short *>(feats), pair_in,
+                         wg_k, reinterpret_cast<const unsigned short *>(wt), contrib);
+    });
+  });
+  return rc;
 }
 
 extern "C" int link_conv_centre_sum_amp(const void *feats, const void *wt, int32_t centre, const void *contrib,
@@ -703,21 +650,20 @@ extern "C" int link_conv_centre_sum_amp(const void *feats, const void *wt, int32
   if (io_dtype != LINK_IO_F16 && io_dtype != LINK_IO_BF16) return LINK_ERR_ARG;
   if (contrib_dtype != LINK_IO_F32 && contrib_dtype != io_dtype) return LINK_ERR_ARG;
   const bool c16 = contrib_dtype != LINK_IO_F32;
-  if (n < 0 || centre < 0 || !link_conv_pairs_supported(cin, cout) || (ln_w == nullptr) != (ln_b == nullptr)) return LINK_ERR_ARG;
-  if (contrib_rows < 0 || contrib_rows * (int64_t)cout * 4 >= 0xFFFFFFF0LL) return LINK_ERR_ARG;   // 32-bit row offsets
+  if (!centre_sum_ok(n, centre, cin, cout, ln_w, ln_b, contrib_rows)) return LINK_ERR_ARG;
   const uint32_t cbytes = (uint32_t)(contrib_rows * cout * (c16 ? 2 : 4));
   if (n == 0) return LINK_OK;
   if (!feats || !wt || !ext_start || !out || (contrib_rows > 0 && (!contrib || !ext_list))) return LINK_ERR_ARG;
-  hipStream_t st = S(stream);
-#define LINK_CA(I, O, M) launch_centre_sum<I, O, M>(feats, (int)io_dtype, wt, centre, contrib, cbytes, ext_start, ext_list, n, bias, ln_w, ln_b, eps, addend, (int)relu, out, st)
-#define LINK_CC(I, O)                                                                                                   \
-  if (cin == I && cout == O)                                                                                            \
-    return io_dtype == LINK_IO_BF16 ? (c16 ? LINK_CA(I, O, 4) : LINK_CA(I, O, 2)) : (c16 ? LINK_CA(I, O, 3) : LINK_CA(I, O, 1))
-  LINK_CC(16, 16); LINK_CC(32, 32); LINK_CC(64, 64); LINK_CC(128, 128);
-  LINK_CC(16, 32); LINK_CC(32, 16); LINK_CC(32, 64); LINK_CC(64, 32); LINK_CC(64, 128); LINK_CC(128, 64);
-  LINK_CC(16, 64); LINK_CC(64, 16);
-#undef LINK_CC
-  return LINK_ERR_ARG;
+  int rc = LINK_ERR_ARG;
+  dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+    return dispatch_bool2(io_dtype == LINK_IO_BF16, c16, [&](auto bf, auto h) {
+      constexpr int MM = (decltype(bf)::value ? 2 : 1) + (decltype(h)::value ? 2 : 0);
+      rc = launch_centre_sum<decltype(ci)::value, decltype(co)::value, MM>(feats, (int)io_dtype, wt, centre, contrib, cbytes, ext_start,
+                                                                           ext_list, n, bias, ln_w, ln_b, eps, addend, (int)relu, out,
+                                                                           S(stream));
+    });
+  });
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1274,19 +1220,6 @@ __global__ void __launch_bounds__(256) k_conv_pairs_wgrad_sum(const float *__res
   gw[(int64_t)k * elems + e] = s;
 }
 
-template <int CI, int CO>
-static int launch_pairs_wgrad(const float *feats, const float *gout, const int32_t *pair_in, const int32_t *pair_out,
-                              const int32_t *wg_k, int64_t granules, int64_t plan_granules, int centre, int64_t n_rows,
-                              float *partial, hipStream_t st) {
-  const size_t lds = (size_t)128 * ((CI + 16) + (CO + 16)) * sizeof(float);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_pairs_wgrad<CI, CO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_conv_pairs_wgrad<CI, CO>), dim3((unsigned)((granules + WGRAD_RUN - 1) / WGRAD_RUN)), dim3(64 * (CI / 16)), lds,
-                     st, feats, gout, pair_in, pair_out, wg_k, granules, plan_granules, centre, n_rows, partial);
-  return check_launch("link_conv_pairs_wgrad");
-}
-
 extern "C" int link_conv_pairs_wgrad(const float *feats, const float *gout, const int32_t *pair_in, const int32_t *pair_out,
                                      const int32_t *wg_k, const int32_t *gran_start, int64_t rows_pad, int32_t kvol,
                                      int64_t n_direct, int32_t cin, int32_t cout, float *partial, float *gw, void *stream) {
@@ -1299,16 +1232,15 @@ extern "C" int link_conv_pairs_wgrad(const float *feats, const float *gout, cons
   if (gr > 0) {
     if (!feats || !gout || !partial || (pg > 0 && (!pair_in || !pair_out || !wg_k))) return LINK_ERR_ARG;
     rc = LINK_ERR_ARG;
-#define LINK_CW(I, O) \
-  if (cin == I && cout == O) rc = launch_pairs_wgrad<I, O>(feats, gout, pair_in, pair_out, wg_k, gr, pg, (int)(kvol / 2), n_direct, partial, st)
-    LINK_CW(16, 16); LINK_CW(32, 32); LINK_CW(64, 64); LINK_CW(128, 128);
-    LINK_CW(16, 32); LINK_CW(32, 16); LINK_CW(32, 64); LINK_CW(64, 32); LINK_CW(64, 128); LINK_CW(128, 64);
-    LINK_CW(16, 64); LINK_CW(64, 16);
-#undef LINK_CW
+    dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {
+      constexpr int CI = decltype(ci)::value, CO = decltype(co)::value;
+      rc = launch_kernel(k_conv_pairs_wgrad<CI, CO>, dim3((unsigned)((gr + WGRAD_RUN - 1) / WGRAD_RUN)), dim3(64 * (CI / 16)),
+                         (size_t)128 * ((CI + 16) + (CO + 16)) * sizeof(float), st, "link_conv_pairs_wgrad", feats, gout, pair_in, pair_out, wg_k,
+                         gr, pg, (int)(kvol / 2), n_direct, partial);
+    });
     if (rc != LINK_OK) return rc;
   }
   const int elems = cin * cout;
-  hipLaunchKernelGGL(k_conv_pairs_wgrad_sum, dim3((unsigned)((elems + 255) / 256), (unsigned)kvol), dim3(256), 0, st, partial, gran_start,
-                     (int)kvol, elems, n_direct > 0 ? (int)(kvol / 2) : -1, (int)pg, (int)gr, gw);
-  return check_launch("link_conv_pairs_wgrad_sum");
+  return launch_kernel(k_conv_pairs_wgrad_sum, dim3((unsigned)((elems + 255) / 256), (unsigned)kvol), dim3(256), 0, st, "link_conv_pairs_wgrad_sum",
+                       partial, gran_start, (int)kvol, elems, n_direct > 0 ? (int)(kvol / 2) : -1, (int)pg, (int)gr, gw);
 }

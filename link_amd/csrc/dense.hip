@@ -17,6 +17,7 @@
 //                        cell instead of 27; all addresses are arithmetic, no lookups.
 // The per-voxel de-modulation + LayerNorm is section C's k_voxel_demod_ln_g fed with vrec/vcell.
 #include "dense_gather.h"
+#include "dispatch.h"
 
 using namespace link;
 
@@ -221,21 +222,13 @@ static int launch_dc_premix(const float *feats, const int32_t *coords, const flo
   int64_t tpw = (tiles + cap - 1) / cap;
   int64_t waves = (tiles + tpw - 1) / tpw;
   int64_t wgs = (waves + 3) / 4;
-  if (lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_insert<C, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_insert<C, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  if (insert)
-    hipLaunchKernelGGL((k_dc_premix_insert<C, true>), dim3((unsigned)wgs), dim3(256), lds, st, feats,
-                       reinterpret_cast<const int4 *>(coords), w_pre, ln_w, ln_b, n, eps, g, fin, cnt,
-                       reinterpret_cast<int4 *>(slots), reinterpret_cast<int4 *>(vrec), vcell, hdr);
-  else
-    hipLaunchKernelGGL((k_dc_premix_insert<C, false>), dim3((unsigned)wgs), dim3(256), lds, st, feats,
-                       reinterpret_cast<const int4 *>(coords), w_pre, ln_w, ln_b, n, eps, g, fin, cnt,
-                       reinterpret_cast<int4 *>(slots), reinterpret_cast<int4 *>(vrec), vcell, hdr);
-  return check_launch("link_dc_premix_insert");
+  int rc = LINK_ERR_ARG;
+  dispatch_bool(insert, [&](auto ins) {
+    rc = launch_kernel(k_dc_premix_insert<C, decltype(ins)::value>, dim3((unsigned)wgs), dim3(256), lds, st, "link_dc_premix_insert", feats,
+                       reinterpret_cast<const int4 *>(coords), w_pre, ln_w, ln_b, n, eps, g, fin, cnt, reinterpret_cast<int4 *>(slots),
+                       reinterpret_cast<int4 *>(vrec), vcell, hdr);
+  });
+  return rc;
 }
 
 
@@ -705,12 +698,8 @@ static int launch_dc_gather(const link_dc_grid_t &g, hipStream_t st, const float
   if (zsplit > g.dim[2]) zsplit = g.dim[2];
   const int64_t nwg = (int64_t)txn * tyn * g.dim[3] * zsplit;
   const int64_t grid = (nwg + 7) / 8 * 8;
-  if (K::LDS_BYTES > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather<C, P, R>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-  hipLaunchKernelGGL((k_dc_gather<C, P, R>), dim3((unsigned)grid), dim3(256), K::LDS_BYTES, st, S_, cell_n, g, txn,
-                     tyn, zsplit, (int)nwg, A);
-  return check_launch("link_dc_gather");
+  return launch_kernel(k_dc_gather<C, P, R>, dim3((unsigned)grid), dim3(256), K::LDS_BYTES, st, "link_dc_gather", S_, cell_n, g, txn, tyn, zsplit,
+                       (int)nwg, A);
 }
 
 template <int C>

@@ -9,6 +9,7 @@
 
 #include "dense_gather.h"
 #include "dense_io.h"
+#include "dispatch.h"
 
 namespace DC_IO_NS {
 using namespace link;
@@ -29,14 +30,9 @@ static int launch_k1p(const link_dc_buffers_t *b, const link_dc_grid_t &g, const
   // tune.k1_lds_pad: extra dynamic LDS requested on purpose (frames in flight): a workgroup that cannot share its CU with a
   // second one of its own kind shares it with the other frame's gather kernel instead -- the better mix (bench.py)
   const int lds_k1 = K::LDS_BYTES + k1_pad <= 160 * 1024 ? K::LDS_BYTES + k1_pad : K::LDS_BYTES;
-  if (lds_k1 > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_modsum<C, OP, NB, PIPE, WB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_k1);
-  hipLaunchKernelGGL((k_dc_premix_modsum<C, OP, NB, PIPE, WB>), dim3((unsigned)wgs), dim3(64 * K::NW), lds_k1, st, b->feats,
-                     reinterpret_cast<int4 *>(b->slots), b->cnt, b->cell_n, b->w_pre, b->pre_ln_w, b->pre_ln_b,
-                     b->w_pos, b->alpha, d.cg, d.coord_div, d.eps, n, g, cpw, warm, b->S, b->fin, b->hdr,
-                     reinterpret_cast<unsigned long long *>(b->tune.k1_dbg));
-  return check_launch("link_dc_premix_modsum");
+  return launch_kernel(k_dc_premix_modsum<C, OP, NB, PIPE, WB>, dim3((unsigned)wgs), dim3(64 * K::NW), lds_k1, st, "link_dc_premix_modsum", b->feats,
+                       reinterpret_cast<int4 *>(b->slots), b->cnt, b->cell_n, b->w_pre, b->pre_ln_w, b->pre_ln_b, b->w_pos, b->alpha, d.cg,
+                       d.coord_div, d.eps, n, g, cpw, warm, b->S, b->fin, b->hdr, reinterpret_cast<unsigned long long *>(b->tune.k1_dbg));
 }
 
 // wb = false: the caller knows that the quad-consumer gather kernel reads this call's records (any order serves it) -- the kernel
@@ -909,34 +905,22 @@ static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const 
   const bool two_part = d.op == LINK_OP_COS || d.op == LINK_OP_SIN;
   const bool pair = d.c == 2 * d.cg && two_part;
   const bool div = d.coord_div != 1.0f;
-#define LINK_K2S(PP, DD)                                                                                              \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather_demod_split<OP, R, PP, DD>),                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, K2::SPLIT_LDS_BYTES + k2_pad);        \
-    hipLaunchKernelGGL((k_dc_gather_demod_split<OP, R, PP, DD>), dim3((unsigned)grid), dim3(512), K2::SPLIT_LDS_BYTES + k2_pad, st, \
-                       b->S, b->cell_n, reinterpret_cast<const int4 *>(b->slots), b->fin, b->w_pos, b->alpha, b->ln_w, \
-                       b->ln_b, d.cg, d.coord_div, d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out, k2_single,       \
-                       reinterpret_cast<unsigned long long *>(b->tune.k2_dbg));                                       \
-  } while (0)
+  const char *what = "link_dc_gather_demod";
+  const int4 *slots = reinterpret_cast<const int4 *>(b->slots);
+  unsigned long long *dbg = reinterpret_cast<unsigned long long *>(b->tune.k2_dbg);
+  int rc = LINK_ERR_ARG;
   // k2_form 0 = by measurement (tools/k2ab.py, cfg2-sized frames): the producer / consumer form where two of its workgroups fit
   // a CU (two-part rows: 29.9 us, own-cell 29.9, single-role 30.4); three-part rows (cos_x) r = 3: own-cell 38.2 us against
   // 53.5 for the single-role kernel (81 KB plane ring: one workgroup per CU); r = 2: single-role 32.9, own-cell 34.4
   const bool own = (b->tune.k2_form & 4) || (!(b->tune.k2_form & 1) && !K2::SPLIT_FITS && R == 3);
   if (own) {                                           // own-cell form: 5 waves, 2-slot ring fed by a dedicated DMA wave
     using KO = dc_k2o_cfg<OP, R>;
-#define LINK_K2O(PP, DD)                                                                                              \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather_demod_own<OP, R, PP, DD>),                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, KO::LDS_BYTES + k2_pad);                   \
-    hipLaunchKernelGGL((k_dc_gather_demod_own<OP, R, PP, DD>), dim3((unsigned)grid), dim3(320), KO::LDS_BYTES + k2_pad, st, b->S, \
-                       b->cell_n, reinterpret_cast<const int4 *>(b->slots), b->fin, b->w_pos, b->alpha, b->ln_w,      \
-                       b->ln_b, d.cg, d.coord_div, d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out,                   \
-                       reinterpret_cast<unsigned long long *>(b->tune.k2_dbg));                                       \
-  } while (0)
-    if (pair) { if (div) LINK_K2O(true, true); else LINK_K2O(true, false); }
-    else { if (div) LINK_K2O(false, true); else LINK_K2O(false, false); }
-#undef LINK_K2O
-    return check_launch("link_dc_gather_demod");
+    dispatch_bool2(pair, div, [&](auto pp, auto dd) {
+      rc = launch_kernel(k_dc_gather_demod_own<OP, R, decltype(pp)::value, decltype(dd)::value>, dim3((unsigned)grid), dim3(320),
+                         KO::LDS_BYTES + k2_pad, st, what, b->S, b->cell_n, slots, b->fin, b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg, d.coord_div,
+                         d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out, dbg);
+    });
+    return rc;
   }
   if constexpr (dc_k2q_cfg<OP, R>::FITS) {             // two-part rows, theta shared by channels j / j + 32: quad consumers (bit 3: round-2 pair form)
     if (k2_takes_quads<OP, R>(b, d)) {
@@ -952,38 +936,28 @@ static int launch_k2(const link_dc_buffers_t *b, const link_dc_grid_t &g, const 
       }
       if (zq > g.dim[2]) zq = g.dim[2];
       const int64_t nwg_q = tiles * zq, grid_q = (nwg_q + 7) / 8 * 8;
-#define LINK_K2Q(DD)                                                                                                  \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather_demod_quad<OP, R, DD>),                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, KQ::LDS_BYTES + k2_pad);                   \
-    hipLaunchKernelGGL((k_dc_gather_demod_quad<OP, R, DD>), dim3((unsigned)grid_q), dim3(KQ::THREADS), KQ::LDS_BYTES + k2_pad, st, b->S, \
-                       b->cell_n, reinterpret_cast<const int4 *>(b->slots), b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg, \
-                       d.coord_div, d.eps, n, g, tq.txn, tq.tyn, zq, (int)nwg_q, b->out,                               \
-                       reinterpret_cast<unsigned long long *>(b->tune.k2_dbg));                                       \
-  } while (0)
-      if (div) LINK_K2Q(true); else LINK_K2Q(false);
-#undef LINK_K2Q
-      return check_launch("link_dc_gather_demod");
+      dispatch_bool(div, [&](auto dd) {
+        rc = launch_kernel(k_dc_gather_demod_quad<OP, R, decltype(dd)::value>, dim3((unsigned)grid_q), dim3(KQ::THREADS), KQ::LDS_BYTES + k2_pad, st,
+                           what, b->S, b->cell_n, slots, b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg, d.coord_div, d.eps, n, g, tq.txn, tq.tyn, zq,
+                           (int)nwg_q, b->out, dbg);
+      });
+      return rc;
     }
   }
   if (!(b->tune.k2_form & 1) && K2::SPLIT_FITS) {
-    if (pair) { if (div) LINK_K2S(true, true); else LINK_K2S(true, false); }
-    else { if (div) LINK_K2S(false, true); else LINK_K2S(false, false); }
-    return check_launch("link_dc_gather_demod");
+    dispatch_bool2(pair, div, [&](auto pp, auto dd) {
+      rc = launch_kernel(k_dc_gather_demod_split<OP, R, decltype(pp)::value, decltype(dd)::value>, dim3((unsigned)grid), dim3(512),
+                         K2::SPLIT_LDS_BYTES + k2_pad, st, what, b->S, b->cell_n, slots, b->fin, b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg,
+                         d.coord_div, d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out, k2_single, dbg);
+    });
+    return rc;
   }
-#undef LINK_K2S
-#define LINK_K2(PP, DD)                                                                                               \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_gather_demod<OP, R, PP, DD>),                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, K2::LDS_BYTES);                             \
-    hipLaunchKernelGGL((k_dc_gather_demod<OP, R, PP, DD>), dim3((unsigned)grid), dim3(256), K2::LDS_BYTES, st, b->S,  \
-                       b->cell_n, reinterpret_cast<const int4 *>(b->slots), b->fin, b->w_pos, b->alpha, b->ln_w,      \
-                       b->ln_b, d.cg, d.coord_div, d.eps, n, g, txn, tyn, zsplit, (int)nwg, b->out, k2_single);     \
-  } while (0)
-  if (pair) { if (div) LINK_K2(true, true); else LINK_K2(true, false); }
-  else { if (div) LINK_K2(false, true); else LINK_K2(false, false); }
-#undef LINK_K2
-  return check_launch("link_dc_gather_demod");
+  dispatch_bool2(pair, div, [&](auto pp, auto dd) {
+    rc = launch_kernel(k_dc_gather_demod<OP, R, decltype(pp)::value, decltype(dd)::value>, dim3((unsigned)grid), dim3(256), K2::LDS_BYTES, st, what,
+                       b->S, b->cell_n, slots, b->fin, b->w_pos, b->alpha, b->ln_w, b->ln_b, d.cg, d.coord_div, d.eps, n, g, txn, tyn, zsplit,
+                       (int)nwg, b->out, k2_single);
+  });
+  return rc;
 }
 
 int run_premix_modsum(const link_dc_buffers_t *b, const link_dc_grid_t &g, const link_elk_desc_t &d, int64_t n,

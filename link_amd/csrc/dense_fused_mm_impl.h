@@ -629,14 +629,9 @@ static int launch_k1m(const link_dc_buffers_t *b, const link_dc_grid_t &g, const
   int pad = b->tune.k1_lds_pad;
   pad = pad < 0 ? 0 : (pad > 16384 ? 16384 : pad);
   const int lds = K::LDS_BYTES + pad <= 160 * 1024 ? K::LDS_BYTES + pad : K::LDS_BYTES;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dc_premix_modsum_mm<C, OP, NB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((k_dc_premix_modsum_mm<C, OP, NB>), dim3((unsigned)wgs), dim3(64 * K::NW), lds, st, b->feats,
-                     reinterpret_cast<int4 *>(b->slots), b->cnt, b->cell_n, b->w_pre, b->pre_ln_w, b->pre_ln_b, b->w_pos,
-                     b->alpha, d.cg, d.coord_div, d.eps, n, g, cpw, warm, b->S, b->fin, b->hdr,
-                     reinterpret_cast<unsigned long long *>(b->tune.k1_dbg));
-  return check_launch("link_dc_premix_modsum");
+  return launch_kernel(k_dc_premix_modsum_mm<C, OP, NB>, dim3((unsigned)wgs), dim3(64 * K::NW), lds, st, "link_dc_premix_modsum", b->feats,
+                       reinterpret_cast<int4 *>(b->slots), b->cnt, b->cell_n, b->w_pre, b->pre_ln_w, b->pre_ln_b, b->w_pos, b->alpha, d.cg,
+                       d.coord_div, d.eps, n, g, cpw, warm, b->S, b->fin, b->hdr, reinterpret_cast<unsigned long long *>(b->tune.k1_dbg));
 }
 
 template <int C, int OP>

@@ -12,9 +12,9 @@
 
 namespace link {
 
-template <int V, class F>
+template <auto V, class F>
 inline bool dispatch_call(F &f) {
-  using arg = std::integral_constant<int, V>;
+  using arg = std::integral_constant<decltype(V), V>;
   if constexpr (std::is_void_v<decltype(f(arg{}))>) { f(arg{}); return true; }
   else return f(arg{});
 }
@@ -24,6 +24,16 @@ inline bool dispatch_int(int v, F &&f) {
   bool ok = false;
   (void)((v == Vs && ((ok = dispatch_call<Vs>(f)), true)) || ...);
   return ok;
+}
+
+// a two-valued template argument: the lambda gets std::bool_constant
+template <class F>
+inline bool dispatch_bool(bool b, F &&f) { return b ? dispatch_call<true>(f) : dispatch_call<false>(f); }
+
+// two of them: the lambda gets (a, b)
+template <class F>
+inline bool dispatch_bool2(bool a, bool b, F &&f) {
+  return dispatch_bool(a, [&](auto ta) { return dispatch_bool(b, [&](auto tb) { return f(ta, tb); }); });
 }
 
 // lanes per feature row of the group kernels, 4 channels (16 B) a lane: pow2ceil(c / 4), at least 4 (narrower rows idle
@@ -53,5 +63,42 @@ inline bool dispatch_radius(int r, F &&f) { return dispatch_int<1, 2, 3>(r, f); 
 // row type at a kernel boundary (row_io.h)
 template <class F>
 inline bool dispatch_row_io(int io_dtype, F &&f) { return dispatch_int<LINK_IO_F32, LINK_IO_F16, LINK_IO_BF16>(io_dtype, f); }
+
+// ---- (cin, cout) width pairs of the sparse convolution ----
+// A pair travels through dispatch_int as cin * 256 + cout; the lambda is called with two integral constants, (cin, cout).
+// Each kernel family's list stands here once: its "supported" predicate is a dispatch with an empty lambda.
+constexpr int wp(int cin, int cout) { return cin * 256 + cout; }
+
+template <int... Ps, class F>
+inline bool dispatch_pair(int cin, int cout, F &&f) {
+  if (cin <= 0 || cin >= 256 || cout <= 0 || cout >= 256) return false;     // outside the packing's range
+  return dispatch_int<Ps...>(wp(cin, cout), [&](auto p) {
+    constexpr int P = decltype(p)::value;
+    return f(std::integral_constant<int, P / 256>{}, std::integral_constant<int, P % 256>{});
+  });
+}
+
+// pair-list form (conv_pairs.hip): gemm, centre-sum and weight-gradient kernels
+template <class F>
+inline bool dispatch_conv_pairs(int cin, int cout, F &&f) {
+  return dispatch_pair<wp(16, 16), wp(32, 32), wp(64, 64), wp(128, 128), wp(16, 32), wp(32, 16), wp(32, 64), wp(64, 32),
+                       wp(64, 128), wp(128, 64), wp(16, 64), wp(64, 16)>(cin, cout, f);
+}
+
+// table form (conv.hip, k_subm_conv_mfma): the square widths, then the channel changes of the reference encoders
+// (cs = [32,32,64,128,256,256,128,96,96] x cr, linkunet.py:262)
+template <class F>
+inline bool dispatch_conv_table(int cin, int cout, F &&f) {
+  return dispatch_pair<wp(16, 16), wp(32, 32), wp(48, 48), wp(64, 64), wp(80, 80), wp(96, 96), wp(112, 112), wp(128, 128),
+                       wp(16, 32), wp(32, 16), wp(32, 64), wp(64, 32), wp(64, 128), wp(128, 64), wp(96, 128), wp(128, 96),
+                       wp(64, 96), wp(96, 64), wp(32, 96), wp(96, 32), wp(16, 64), wp(64, 16), wp(32, 128), wp(128, 32)>(
+      cin, cout, f);
+}
+
+// resident-weights kernels (conv.hip): every W_k of the layer fits in LDS
+template <class F>
+inline bool dispatch_conv_resident(int cin, int cout, F &&f) {
+  return dispatch_pair<wp(16, 16), wp(32, 32), wp(16, 32), wp(32, 16)>(cin, cout, f);
+}
 
 }  // namespace link

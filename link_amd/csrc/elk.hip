@@ -127,15 +127,8 @@ static int launch_premix_tlp(const void *feats, const float *w_pre, const float 
   int64_t tiles = (n + 15) / 16;
   int64_t wgs = (tiles + 3) / 4;
   if (wgs > g_premix_wgs) wgs = g_premix_wgs;
-  if (lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in once per kernel (160 KB per CU on gfx950)
-    // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
-    // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_tlp<C, IO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL((k_premix_ln_tlp<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, ln_b, n,
-                     eps, fin, (g_wt & 1) != 0 && wt_ok(n, C));
-  return check_launch("link_premix_ln");
+  return launch_kernel(k_premix_ln_tlp<C, IO>, dim3((unsigned)wgs), dim3(256), lds, st, "link_premix_ln", feats, w_pre, ln_w, ln_b, n, eps, fin,
+                       (g_wt & 1) != 0 && wt_ok(n, C));
 }
 
 // the MFMA kernel for the row widths and row types it is built for (the one place both are chosen); false: c is none of them

@@ -6,13 +6,10 @@ using namespace link;
 
 template <int C, int OP, int NB>
 static void launch_lean_a(const lean_args &a, int64_t n_prev, hipStream_t st) {
-  const int lds = dc_wimg<C>::W_BYTES;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lean_insert_premix<C, OP, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   // the frame's workgroups, then (indexed steps) 256 item slots of the previous frame per workgroup to clean its counters
   const int64_t wgs = (int64_t)a.nwg + (a.build ? ((int64_t)LEAN_SEGS * a.idx_cap_prev + 255) / 256 : 0);
   if (wgs < 1) return;
-  hipLaunchKernelGGL((k_lean_insert_premix<C, OP, NB>), dim3((unsigned)wgs), dim3(256), lds, st, a);
+  launch_kernel_unchecked(k_lean_insert_premix<C, OP, NB>, dim3((unsigned)wgs), dim3(256), dc_wimg<C>::W_BYTES, st, a);
 }
 
 // which form of launch 1: the channel-split form (16 voxels per workgroup) where a frame is too small to fill the chip with
@@ -62,10 +59,7 @@ static bool lean_use_pm(const link_elk_desc_t &d, int64_t n) {
 
 template <int C, int OP, int NB>
 static void launch_lean_pm(const lean_args &a, hipStream_t st) {
-  const int lds = dc_wimg<C>::W_BYTES;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lean_sums_pm<C, OP, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((k_lean_sums_pm<C, OP, NB>), dim3(lean_item_wgs(a.idx_cap)), dim3(256), lds, st, a);
+  launch_kernel_unchecked(k_lean_sums_pm<C, OP, NB>, dim3(lean_item_wgs(a.idx_cap)), dim3(256), dc_wimg<C>::W_BYTES, st, a);
 }
 
 template <int C, int OP>

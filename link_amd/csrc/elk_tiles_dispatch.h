@@ -26,13 +26,9 @@ static int launch_tiles(const void *feats, const int32_t *vox_sorted, const int3
                         const float *alpha, const link_elk_desc_t &d, int64_t n, int64_t m_cap, float *S_, int64_t s_bytes,
                         float *fin, hipStream_t st) {
   using K = elk_t_cfg<C, OP>;
-  const int lds = K::LDS_BYTES;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_elk_tiles<C, OP, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((k_elk_tiles<C, OP, NB>), dim3((unsigned)tiles_wgs(n)), dim3(64 * K::NW), lds, st, feats,
-                     reinterpret_cast<const int4 *>(vox_sorted), pos_blk, blk_start, hdr, w_pre, ln_w, ln_b, w_pos, alpha, d.cg,
-                     d.coord_div, d.eps, n, m_cap, tiles_span(n), S_, (uint32_t)s_bytes, (uint32_t)elk_t_part_off(m_cap, K::P * C), fin);
-  return check_launch("link_elk_premix_modsum_tiles");
+  return launch_kernel(k_elk_tiles<C, OP, NB>, dim3((unsigned)tiles_wgs(n)), dim3(64 * K::NW), K::LDS_BYTES, st, "link_elk_premix_modsum_tiles", feats,
+                       reinterpret_cast<const int4 *>(vox_sorted), pos_blk, blk_start, hdr, w_pre, ln_w, ln_b, w_pos, alpha, d.cg, d.coord_div,
+                       d.eps, n, m_cap, tiles_span(n), S_, (uint32_t)s_bytes, (uint32_t)elk_t_part_off(m_cap, K::P * C), fin);
 }
 
 template <int C, int OP, typename... A>
@@ -75,13 +71,9 @@ static int launch_gather(const float *S_, const float *fin, const int32_t *vox_s
   using K = elk_g_cfg<C, OP, R>;
   // a multiple of 8: the kernel deals contiguous eighths of the tiles to the XCDs (workgroup w runs on XCD w % 8)
   const int64_t wgs = ((n + (int64_t)K::WP * K::NW - 1) / ((int64_t)K::WP * K::NW) + 7) & ~(int64_t)7;
-  if (K::LDS_BYTES > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_elk_gather_tiles<C, OP, R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              K::LDS_BYTES);
-  hipLaunchKernelGGL((k_elk_gather_tiles<C, OP, R>), dim3((unsigned)wgs), dim3(64 * K::NW), K::LDS_BYTES, st, S_, fin,
-                     reinterpret_cast<const int4 *>(vox_sorted), pos_blk, reinterpret_cast<const int4 *>(blk_coords), cell_blk, g, hdr,
-                     w_pos, alpha, ln_w, ln_b, d.cg, d.coord_div, d.eps, m_cap, out);
-  return check_launch("link_elk_gather_demod_tiles");
+  return launch_kernel(k_elk_gather_tiles<C, OP, R>, dim3((unsigned)wgs), dim3(64 * K::NW), K::LDS_BYTES, st, "link_elk_gather_demod_tiles", S_, fin,
+                       reinterpret_cast<const int4 *>(vox_sorted), pos_blk, reinterpret_cast<const int4 *>(blk_coords), cell_blk, g, hdr, w_pos,
+                       alpha, ln_w, ln_b, d.cg, d.coord_div, d.eps, m_cap, out);
 }
 
 template <int C, typename... A>

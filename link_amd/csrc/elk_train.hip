@@ -401,15 +401,8 @@ static int launch_premix_bwd(const void *feats, const float *w_pre, const float 
                              int64_t n, float eps, float *g_pre, void *g_feats, float *partials, int wgs,
                              hipStream_t st) {
   size_t lds = ((size_t)2 * C * (C + 4) + 8 * C) * sizeof(float);
-  if (lds > 64 * 1024) {
-    // per device and cheap (a host-side table write): no process-wide once-flag, which a second GPU or a
-    // device reset would never pass again
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_premix_ln_bwd<C, IO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL((k_premix_ln_bwd<C, IO>), dim3((unsigned)wgs), dim3(256), lds, st, feats, w_pre, ln_w, g_fin, n, eps,
-                     g_pre, g_feats, partials);
-  return check_launch("link_premix_ln_backward");
+  return launch_kernel(k_premix_ln_bwd<C, IO>, dim3((unsigned)wgs), dim3(256), lds, st, "link_premix_ln_backward", feats, w_pre, ln_w, g_fin, n, eps,
+                       g_pre, g_feats, partials);
 }
 
 // the one place the width and the row type of the pre_mix backward are chosen; the callers have checked both

@@ -1,5 +1,6 @@
 """Tables, rows and the case lattice of tests/test_gpu_conv_lattice.py, and a pure-Python restatement of which kernel instance a
 sparse-convolution call reaches (csrc/conv.hip: subm_conv_impl, launch_conv_mfma, launch_conv_mfma_nt, launch_conv_resident;
+csrc/dispatch.h: the width lists dispatch_conv_resident, dispatch_conv_table, dispatch_conv_pairs;
 link_amd/elk.py: subm_conv, subm_conv_ln_add_relu, _conv_pairs, _conv_weight_grad).  No GPU code: tests/test_cpu_conv_frames.py
 checks every claim made here (counts, routes, coverage, the constants against the sources) without a device.
 
@@ -29,13 +30,13 @@ DENSITY = 0.3
 # ------------------------------------------------------------------------------------------------------------------------------
 G_CONV_WGS = 1024                              # conv.hip: g_conv_wgs
 LDS_LIMIT = 160 * 1024
-RESIDENT = ((16, 16), (32, 32), (16, 32), (32, 16))                    # conv.hip: launch_conv_resident<...>; elk.py: _RESIDENT_SHAPES
+RESIDENT = ((16, 16), (32, 32), (16, 32), (32, 16))                    # dispatch.h: dispatch_conv_resident; elk.py: _RESIDENT_SHAPES
 LINK_CONV = ((16, 16), (32, 32), (48, 48), (64, 64), (80, 80), (96, 96), (112, 112), (128, 128),
              (16, 32), (32, 16), (32, 64), (64, 32), (64, 128), (128, 64),
              (96, 128), (128, 96), (64, 96), (96, 64), (32, 96), (96, 32),
-             (16, 64), (64, 16), (32, 128), (128, 32))                 # conv.hip: the LINK_CONV(I, O) list
+             (16, 64), (64, 16), (32, 128), (128, 32))                 # dispatch.h: dispatch_conv_table
 MFMA = tuple(p for p in LINK_CONV if p not in RESIDENT)                 # (the resident test comes first: its four pairs never get there)
-PAIRS_SQUARE = (16, 32, 64, 128)                                        # conv_pairs.hip: link_conv_pairs_supported
+PAIRS_SQUARE = (16, 32, 64, 128)                                        # dispatch.h: dispatch_conv_pairs (link_conv_pairs_supported)
 PAIRS_RECT = ((16, 32), (32, 16), (32, 64), (64, 32), (64, 128), (128, 64), (16, 64), (64, 16))
 PAIR_DENSITY_MAX = 17.0                                                 # elk.py
 WGRAD_CHUNK_EDGES = (16000, 60000)                                      # elk.py: chunks 16 / 32 / 64
@@ -109,9 +110,10 @@ def route(n_out, cin, cout, kvol, epilogue=False, form="table", half=False, dens
     return _route_table(n_out, cin, cout, kvol, epilogue)
 
 
-def route_wgrad(n_out, cin, cout, kvol, link_subm=False, density=None, direct=None):
-    """_conv_weight_grad: the table kernel with its (chunks, centre_extra), the pair list, or the torch fallback."""
-    square_small = cin == cout and cin <= 64 and cin % 4 == 0
+def route_wgrad(n_out, cin, cout, kvol, link_subm=False, density=None, direct=None, table_square=True):
+    """_conv_weight_grad: the table kernel with its (chunks, centre_extra), the pair list, or the torch fallback.
+    `table_square`: elk.py's WGRAD_TABLE_SQUARE."""
+    square_small = table_square and cin == cout and cin <= 64 and cin % 4 == 0
     takes_pairs = lambda ci: n_out > 0 and pairs_supported(ci, cout) and kvol <= 64 and density <= PAIR_DENSITY_MAX   # noqa: E731
     if cin < 16 and not square_small and takes_pairs(16):
         cin = 16
@@ -321,6 +323,8 @@ def case_route(c):
 
 N_SMALL = 1007                                                             # 63 tiles, the last one of 15 rows: the DEEP instance
 W_TABLE = ("crafted", N_SMALL, 700, 27, 1)
+SUB_SMALL = ("submlike", N_SMALL, 27, 6)                                   # the same size with the identity centre: a direct pair plan
+PAIRS_FORWARD_REST = ((32, 32), (32, 16), (64, 32), (64, 128), (32, 64))
 
 
 def _lattice():
@@ -360,6 +364,9 @@ def _lattice():
               Case("pairs", real, 128, 128, form, ep="ln"), Case("pairs", ("granule", False), 64, 64, form, ep="ln"),
               Case("pairs", sub, 16, 32, form, ep="ln_add_relu")]
         L += [Case("pairs", sub, 64, 64, form, ep="affine_add_relu", big=True), Case("pairs", crafted, 64, 64, form, ep="ln", big=True)]
+        # the widths of dispatch_conv_pairs that no case above sends through the f32 GEMM and the centre-sum kernel, on a
+        # submanifold-like table of the small size: with them each of the 12 pairs reaches both entry points
+        L += [Case("pairs", SUB_SMALL, ci, co, form) for ci, co in PAIRS_FORWARD_REST]
     L += [Case("pairs", real, 4, 64, "auto"), Case("pairs", real, 64, 3, "auto")]           # padded to 16 channels in / out
     L += [Case("half", sub, 64, 64, "pairs", rows="fp16"), Case("half", crafted, 64, 64, "pairs", rows="fp16"),
           Case("half", sub, 64, 64, "pairs", rows="bf16"), Case("half", real, 32, 64, "pairs", rows="fp16"),
@@ -380,7 +387,10 @@ WGRAD_N = (40, 4095, 4096, 15999, 16000, 60000)
 # (table key, cin, cout): rectangular and wide pairs, direct (submanifold-like / real) and non-direct plans, first-layer padding
 WGRAD_PAIRS = ((("submlike", 2000, 27, 6), 32, 64), (("real", "lidar", 3000), 128, 128), (("crafted", 1500, 900, 27, 7), 64, 128),
                (("crafted", 1500, 900, 27, 7), 128, 128), (("granule", True), 16, 32), (("granule", False), 64, 16),
-               (("real", "lidar", 3000), 4, 64), (("down", "lidar", 3000), 32, 64))
+               (("real", "lidar", 3000), 4, 64), (("down", "lidar", 3000), 32, 64),
+               (SUB_SMALL, 32, 16), (SUB_SMALL, 64, 32), (SUB_SMALL, 128, 64))           # the rectangular widths the rows above leave out
+# the square widths <= 64 reach link_conv_pairs_wgrad only with elk.py's WGRAD_TABLE_SQUARE off (the table kernel has them otherwise)
+WGRAD_PAIRS_SQUARE = ((SUB_SMALL, 16, 16), (SUB_SMALL, 32, 32), (SUB_SMALL, 64, 64))
 WGRAD_TORCH = ((W_TABLE, 6, 10),)
 
 

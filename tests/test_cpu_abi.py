@@ -108,6 +108,39 @@ def test_argument_validation_without_gpu():
     assert lib.link_aux_to_voxel_forward_scatter(*([None] * 4), ctypes.byref(g), None, None, None, 10, 10, 128, 3, None, None, None, None) == L.LINK_ERR_ARG  # null buffers
 
 
+def test_pair_list_width_support_is_one_list():
+    """link_conv_pairs_supported and every pair-list entry point answer from the same width list: at zero rows and with null
+    buffers an unsupported (cin, cout) is LINK_ERR_ARG and a supported one LINK_OK.  link_conv_pairs_wgrad has no zero-row
+    return (it always runs its reduction into gw), so a supported width gets as far as its null check of gw / gran_start, which
+    is LINK_ERR_ARG too: of that entry the test pins the refusal and that nothing is launched."""
+    import conv_frames as CF
+    from link_amd import _lib as L
+    lib = L.lib()
+    ok_rows = {
+        "gemm": lambda ci, co: lib.link_conv_pairs_gemm(None, None, None, 0, None, ci, co, None, None),
+        "gemm_io": lambda ci, co: lib.link_conv_pairs_gemm_io(None, L.IO_F16, None, None, 0, None, ci, co, None, None),
+        "centre_sum": lambda ci, co: lib.link_conv_centre_sum(None, None, 13, None, 0, None, None, 0, ci, co, None, None, None, 0.0,
+                                                              None, 0, None, None),
+        "centre_sum_io": lambda ci, co: lib.link_conv_centre_sum_io(None, None, 13, None, 0, None, None, 0, ci, co, None, None, None,
+                                                                    0.0, None, 0, None, L.IO_BF16, None),
+        "gemm_split": lambda ci, co: lib.link_conv_pairs_gemm_split(None, None, None, 0, None, None, None, ci, co, None, None),
+        "gemm_amp": lambda ci, co: lib.link_conv_pairs_gemm_amp(None, L.IO_BF16, None, None, 0, None, ci, co, None, L.IO_F32, None),
+        "centre_sum_amp": lambda ci, co: lib.link_conv_centre_sum_amp(None, None, 13, None, L.IO_F16, 0, None, None, 0, ci, co, None,
+                                                                      None, None, 0.0, None, 0, None, L.IO_F16, None),
+    }
+    widths = (8, 16, 32, 48, 64, 80, 96, 112, 128, 256)
+    n_ok = 0
+    for ci in widths:
+        for co in widths:
+            sup = lib.link_conv_pairs_supported(ci, co)
+            assert sup == int(CF.pairs_supported(ci, co)), (ci, co)
+            n_ok += sup
+            for name, call in ok_rows.items():
+                assert call(ci, co) == (L.LINK_OK if sup else L.LINK_ERR_ARG), (name, ci, co)
+            assert lib.link_conv_pairs_wgrad(None, None, None, None, None, None, 0, 27, 0, ci, co, None, None, None) == L.LINK_ERR_ARG
+    assert n_ok == 12
+
+
 def test_grid_from_bounds_host_logic():
     from link_amd import _lib as L
     g = L.grid_from_bounds((0, 0, 0, 0), (255, 255, 255, 0), 7)

@@ -34,6 +34,28 @@ def test_the_lattice_reaches_every_branch():
     assert reached - want == set(), sorted(reached - want, key=str)          # and route() names no branch the enumeration lacks
 
 
+def test_every_pair_list_width_reaches_the_gemm_the_centre_sum_and_the_weight_gradient():
+    """Each of the 12 widths of dispatch_conv_pairs is launched through the f32 pair GEMM and the centre-sum kernel (a direct plan
+    runs both) and through link_conv_pairs_wgrad (the square widths up to 64 with WGRAD_TABLE_SQUARE off)."""
+    widths = {(c, c) for c in CF.PAIRS_SQUARE} | set(CF.PAIRS_RECT)
+    assert len(widths) == 12
+    fwd = set()
+    for c in CF.LATTICE:
+        r = CF.case_route(c)
+        if r["kernel"] == "pairs" and r["direct"] and c.rows == "fp32":
+            fwd.add((r["CI"], r["CO"]))
+    assert fwd == widths, widths ^ fwd
+    wg = {(r["CI"], r["CO"]) for _, r in CF.wgrad_routes() if r["kernel"] == "pairs_wgrad"}
+    for tkey, ci, co in CF.WGRAD_PAIRS_SQUARE:
+        nbr, n_in = CF.table(tkey)
+        density, direct = CF.table_stats(nbr, n_in)
+        r = CF.route_wgrad(nbr.shape[0], ci, co, nbr.shape[1], density=density, direct=direct, table_square=False)
+        assert r == dict(kernel="pairs_wgrad", CI=ci, CO=co, direct=True)
+        assert CF.route_wgrad(nbr.shape[0], ci, co, nbr.shape[1])["kernel"] == "table_wgrad"
+        wg.add((ci, co))
+    assert wg == widths, widths ^ wg
+
+
 def test_lattice_ids_are_unique_and_cases_are_what_the_issue_lists():
     ids = [CF.case_id(c) for c in CF.LATTICE]
     assert len(ids) == len(set(ids))
@@ -123,26 +145,47 @@ def test_conv_hip_pins():
         "const bool mfma_ok = (cin & 15) == 0 && (cout & 15) == 0 && cin <= 128 && cout <= 128 && kvol <= 27;",
         "if (mfma_ok && kvol <= 27 && n >= CONV_RESIDENT_MIN) {",
         "const bool split = ep.ln_w != nullptr;",
-        "const int cpl = (cout + 63) / 64;",
         "if (n == 0) return LINK_OK;",
     ):
         assert line in src, line
-    assert tuple((int(a), int(b)) for a, b in re.findall(r"LINK_CONV\((\d+), (\d+)\);", src)) == CF.LINK_CONV
+    # the width lists stand once, in dispatch.h; the launchers hold no literal width
+    assert _width_pairs("dispatch_conv_table") == CF.LINK_CONV
+    assert _width_pairs("dispatch_conv_resident") == CF.RESIDENT
+    assert not re.search(r"cin == \d|LINK_CONV", src)
     impl = src[src.index("static int subm_conv_impl(const float *feats, const int32_t *nbr, const float *w, const int32_t *order,\n"
                          "                          int64_t n, int32_t cin, int32_t cout, int32_t kvol, float *out,\n"
                          "                          const conv_epilogue &ep, void *stream) {"):]
-    assert tuple((int(a), int(b)) for a, b in re.findall(r"return launch_conv_resident<(\d+), (\d+)>\(", impl)) == CF.RESIDENT
-    assert impl.index("launch_conv_resident<") < impl.index("LINK_CONV(16, 16)")          # the resident test comes first
-    assert [int(v) for v in re.findall(r"k_subm_conv_generic<(\d)>, grid", impl)] == [1, 2, 3, 4]
+    impl = impl[:impl.index("\n}\n")]
+    assert impl.count("dispatch_conv_resident(cin, cout,") == 1 and impl.count("dispatch_conv_table(cin, cout,") == 1
+    assert impl.index("launch_conv_resident<") < impl.index("dispatch_conv_table(")       # the resident test comes first
+    assert impl.index("if (resident) return rc;") < impl.index("dispatch_conv_table(")
+    # the generic kernel: channels per lane = (cout + 63) / 64, 1 .. 4
+    assert impl.index("if (table) return rc;") < impl.index("dispatch_cpl(cout, [&](auto cpl) {")
+    assert "k_subm_conv_generic<decltype(cpl)::value>" in impl
+    assert "inline bool dispatch_cpl(int c, F &&f) { return dispatch_int<1, 2, 3, 4>((c + 63) / 64, f); }" in \
+        _src("link_amd", "csrc", "dispatch.h")
+    amp = src[src.index('extern "C" int link_subm_conv_resident_amp('):]
+    assert "dispatch_conv_resident(cin, cout," in amp[:amp.index("\n}\n")]
+
+
+def _width_pairs(wrapper):
+    """The (cin, cout) list of one of dispatch.h's width-pair wrappers, in its order."""
+    src = _src("link_amd", "csrc", "dispatch.h")
+    fn = src[src.index(f"inline bool {wrapper}(int cin, int cout, F &&f) {{"):]
+    fn = fn[:fn.index("\n}\n")]
+    return tuple((int(a), int(b)) for a, b in re.findall(r"wp\((\d+), (\d+)\)", fn))
 
 
 def test_conv_pairs_hip_pins():
     src = _src("link_amd", "csrc", "conv_pairs.hip")
     fn = src[src.index('extern "C" int link_conv_pairs_supported(int32_t cin, int32_t cout) {'):]
     fn = fn[:fn.index("\n}\n")]
-    assert "const bool sq = cin == cout && (cin == 16 || cin == 32 || cin == 64 || cin == 128);" in fn
-    assert tuple((int(a), int(b)) for a, b in re.findall(r"\(cin == (\d+) && cout == (\d+)\)", fn)) == CF.PAIRS_RECT
+    assert "return dispatch_conv_pairs(cin, cout, [](auto, auto) {}) ? 1 : 0;" in fn
+    assert _width_pairs("dispatch_conv_pairs") == tuple((c, c) for c in CF.PAIRS_SQUARE) + CF.PAIRS_RECT
     assert CF.PAIRS_SQUARE == (16, 32, 64, 128)
+    # six launchers, one list: no literal width and no macro ladder is left in the file
+    assert src.count("dispatch_conv_pairs(cin, cout, [&](auto ci, auto co) {") == 6
+    assert not re.search(r"cin == \d|LINK_C[PCWSA]\b", src)
 
 
 def test_elk_py_pins():

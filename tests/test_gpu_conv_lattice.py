@@ -293,6 +293,24 @@ def test_weight_gradient_pair_list_and_fallback(tkey, cin, cout):
     _weight_grad_case(tkey, cin, cout, None, want)
 
 
+@pytest.mark.parametrize("tkey,cin,cout", CF.WGRAD_PAIRS_SQUARE, ids=lambda v: "-".join(str(x) for x in v) if isinstance(v, tuple) else str(v))
+def test_weight_gradient_pair_list_square_widths(tkey, cin, cout, monkeypatch):
+    """link_conv_pairs_wgrad at the square widths up to 64, which _conv_weight_grad gives to the table kernel while
+    WGRAD_TABLE_SQUARE is set: with the switch off they run the pair list, under the same gate as every other width."""
+    import link_amd.elk as E
+    monkeypatch.setattr(E, "WGRAD_TABLE_SQUARE", False)
+    nbr = _table(tkey)
+    f, w, g, g64, o32, A = _grad_ref(tkey, cin, cout)
+    shape = (nbr.shape[1], cin, cout)
+    a = E._conv_weight_grad(f, g, nbr, shape)
+    plan = nbr._link_pairs
+    route = CF.route_wgrad(nbr.shape[0], cin, cout, nbr.shape[1], density=plan.density, direct=plan.direct, table_square=False)
+    _gate_grad(CF.wgrad_label(tkey, cin, cout, False) + ":pairs", route, "kernel", a, g64["kernel"], o32["kernel"], A["kernel"],
+               A["pairs"].double()[:, None, None])
+    assert route == dict(kernel="pairs_wgrad", CI=cin, CO=cout, direct=True), route
+    assert torch.equal(a, E._conv_weight_grad(f, g, nbr, shape)), "second call differs"
+
+
 @pytest.mark.parametrize("cin,cout", [(64, 64), (16, 16), (48, 48), (32, 64), (128, 32)])
 def test_input_gradient_through_submconv(cin, cout):
     """_SubmConv on a real (symmetric) map: g_f = the forward kernels on g_out with the flipped, transposed weights; g_w with it."""
