@@ -89,9 +89,13 @@ int link_voxelize_forward(const float *in, const int32_t *idx, const int32_t *co
 
 /* voxelize_backward_cuda(top fp[N1,c], idx, counts, N) -> fp[N,c]
  *                                             backend/voxelize/voxelize_cuda.cu:28-42,63-80
- * bottom[i] = top[idx[i]] / counts[idx[i]]  (0 where idx[i] < 0). */
+ * bottom[i] = top[idx[i]] / counts[idx[i]]  (0 where idx[i] < 0).  Every idx[i] must be below the length of `counts` (an idx
+ * built with its counts: the block index); link_voxelize_backward_n1 takes that length n1 and gives a zero row to idx[i] >= n1,
+ * the rows link_voxelize_forward skips (voxelize_cuda.cu:38) -- what the drop-in backend function calls. */
 int link_voxelize_backward(const float *top, const int32_t *idx, const int32_t *counts, int64_t n,
                            int64_t c, float *bottom, void *stream);
+int link_voxelize_backward_n1(const float *top, const int32_t *idx, const int32_t *counts, int64_t n,
+                              int64_t c, int64_t n1, float *bottom, void *stream);
 
 /* devoxelize_forward_cuda(feat fp[n,c], ind i32[N,K], w fp[N,K], r) -> fp[N,c],  K = r^3
  *                                             backend/devoxelize/devoxelize_cuda.cu:11-34,63-81

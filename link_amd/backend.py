@@ -118,7 +118,10 @@ def voxelize_backward_cuda(top_grad: torch.Tensor, idx: torch.Tensor, counts: to
     idx, counts = idx.contiguous(), counts.contiguous()
     c = top_grad.shape[1]
     out = torch.empty((int(N), c), dtype=torch.float32, device=top_grad.device)
-    L.check(L.lib().link_voxelize_backward(_p(top_grad), _p(idx), _p(counts), int(N), c, _p(out), _stream()),
+    if idx.dtype != torch.int32 or counts.dtype != torch.int32:
+        raise ValueError("voxelize_backward_cuda expects int32 idx/counts")
+    # idx is the caller's: an entry at or beyond len(counts) gets a zero row, as the forward skips it (voxelize_cuda.cu:22,38)
+    L.check(L.lib().link_voxelize_backward_n1(_p(top_grad), _p(idx), _p(counts), int(N), c, counts.shape[0], _p(out), _stream()),
             "voxelize_backward_cuda")
     return out.to(dt)
 

@@ -276,13 +276,13 @@ extern "C" int link_voxelize_forward(const float *in, const int32_t *idx, const 
 __global__ void __launch_bounds__(256) k_voxelize_bwd(const float *__restrict__ top,
                                                       const int32_t *__restrict__ idx,
                                                       const int32_t *__restrict__ counts, int64_t n,
-                                                      int c, float *__restrict__ bottom) {
+                                                      int c, int64_t n1, float *__restrict__ bottom) {
   int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   int lane = threadIdx.x & 63;
   if (row >= n) return;
   int32_t pos = idx[row];
   float *dst = bottom + row * (int64_t)c;
-  int32_t cn = (pos >= 0) ? counts[pos] : 0;
+  int32_t cn = (pos >= 0 && pos < n1) ? counts[pos] : 0;     // the rows the forward skips (voxelize_cuda.cu:38): zero gradient
   if (cn == 0) {
     for (int j = lane; j < c; j += 64) dst[j] = 0.f;
     return;
@@ -292,14 +292,26 @@ __global__ void __launch_bounds__(256) k_voxelize_bwd(const float *__restrict__ 
   for (int j = lane; j < c; j += 64) dst[j] = src[j] / fc;
 }
 
-extern "C" int link_voxelize_backward(const float *top, const int32_t *idx, const int32_t *counts,
-                                      int64_t n, int64_t c, float *bottom, void *stream) {
-  if (n < 0 || c < 0 || c > (1 << 20)) return LINK_ERR_ARG;
+static int voxelize_backward_impl(const float *top, const int32_t *idx, const int32_t *counts, int64_t n, int64_t c,
+                                  int64_t n1, float *bottom, void *stream, const char *what) {
+  if (n < 0 || c < 0 || n1 < 0 || c > (1 << 20)) return LINK_ERR_ARG;
   if (n == 0 || c == 0) return LINK_OK;
   if (!top || !idx || !counts || !bottom) return LINK_ERR_ARG;
   hipLaunchKernelGGL(k_voxelize_bwd, dim3(blocks_for(n * 64, 256)), dim3(256), 0, S(stream), top, idx,
-                     counts, n, (int)c, bottom);
-  return check_launch("link_voxelize_backward");
+                     counts, n, (int)c, n1, bottom);
+  return check_launch(what);
+}
+
+// idx produced together with counts (the block index: vox_blk / counts_buf), every entry below the length of counts
+extern "C" int link_voxelize_backward(const float *top, const int32_t *idx, const int32_t *counts,
+                                      int64_t n, int64_t c, float *bottom, void *stream) {
+  return voxelize_backward_impl(top, idx, counts, n, c, INT64_MAX, bottom, stream, "link_voxelize_backward");
+}
+
+// a caller's idx: entries at or beyond n1 = the length of counts get a zero row, as the forward skips them
+extern "C" int link_voxelize_backward_n1(const float *top, const int32_t *idx, const int32_t *counts,
+                                         int64_t n, int64_t c, int64_t n1, float *bottom, void *stream) {
+  return voxelize_backward_impl(top, idx, counts, n, c, n1, bottom, stream, "link_voxelize_backward_n1");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -92,6 +92,8 @@ def _voxelize_by_index(cells: torch.Tensor, feats: torch.Tensor):
     idx_query = rank[index.idx_query]
     counts = index.counts[order].contiguous()
     vox_feats = _BlockMean.apply(feats, index)[order]         # means in id order inside a voxel: the same bits every run
+    #   (for voxels of at most 8192 points: csrc/index.hip sorts a longer member list not at all, SORT_MAX_SEG, and leaves it in the order
+    #   its atomics ranked it -- such a voxel's mean agrees to fp32 summation order, not bit for bit)
     return vox_feats, ucoords[order].contiguous(), idx_query, counts, index
 
 

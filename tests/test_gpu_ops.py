@@ -124,3 +124,6 @@ def test_backend_dtype_parity(dt):
     w = rng.random((300, 8)).astype(np.float32)
     dv = B.devoxelize_forward_cuda(out, dev(ind), dev(w).to(dt), 2)
     assert dv.dtype == dt and dv.shape == (300, c)
+    # the values: the dt inputs are the values (widened exactly), fp32 accumulation, the result rounded to dt once
+    ref = O.spdevoxelize_fwd(out.float().cpu().numpy(), ind, dev(w).to(dt).float().cpu().numpy())
+    assert rel_err(dv.float().cpu().numpy(), ref) < tol
