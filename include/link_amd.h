@@ -149,11 +149,14 @@ size_t link_index_scratch_bytes(int64_t n, int64_t v);
  *   cell_blk   i32[V]    block id + 1 of each cell, 0 = empty       (neighbour lookup table)
  *   vox_blk    i32[N]    block id of each voxel                      (== idx_query, utils.py:50)
  *   idx_query  i64[N]    same as int64 (may be NULL)                 (reference dtype)
- *   perm       i32[N]    voxel ids grouped by block, ascending voxel id inside a block
+ *   perm       i32[N]    voxel ids grouped by block, ascending voxel id inside a block of at most 8192 voxels (a longer
+ *                        segment holds the block's ids in the order their atomics ranked them: k_sort_seg, SORT_MAX_SEG)
  *   vox_sorted i32[N,4]  (x, y, z, voxel id) of the voxel at each position of perm: the record the
  *                        fused kernels stream instead of chasing perm -> coords (may be NULL)
  *   pos_blk    i32[N]    block id of the voxel at each position of perm (may be NULL)
- *   blk_start  i32[N+1]  start of each block's segment in perm; blk_start[M] = N
+ *   blk_start  i32[N+1]  start of each block's segment in perm; blk_start[M] = hdr[LINK_HDR_NVALID] (= N when no voxel
+ *                        lies outside the grid; such a voxel gets vox_blk = idx_query = -1 and sets status bit 0, the rest is
+ *                        the index of the voxels inside with their ids kept, perm / pos_blk / vox_sorted valid in [0, NVALID))
  *   blk_coords i32[N,4]  block coordinates, rows [0,M) valid         (== small_x.C, utils.py:47)
  *   counts     i32[N]    voxels per block, rows [0,M) valid          (== spcount, utils.py:51)
  *   hdr        i32[8]    see LINK_HDR_*
@@ -177,7 +180,9 @@ int link_index_build_first(const int32_t *coords, int64_t n, const link_grid_t *
                            int32_t *vox_sorted, int32_t *pos_blk, int32_t *blk_start, int32_t *blk_coords, int32_t *counts,
                            int32_t *hdr, void *stream);
 /* The cell half of link_index_build alone (no voxel placement): sorted unique block coordinates blk_coords i32[.,4],
- * counts, cell table and hdr[LINK_HDR_M] of the rows `coords` -- rows outside the grid are dropped (status word).
+ * counts, cell table and hdr[LINK_HDR_M] of the rows `coords` -- rows outside the grid are dropped SILENTLY: nothing places
+ * the rows here, so no kernel sets the status bit and hdr[LINK_HDR_STATUS] is written 0; hdr[LINK_HDR_NVALID] counts the rows
+ * inside, and NVALID < n is how a caller tells.  (The candidate kernel relies on it: its "no site" row lies outside every grid.)
  * Same scratch / cell_counts contract as link_index_build.  Used for the output-site set of site-creating
  * convolutions, whose candidate rows are mostly duplicates. */
 int link_index_cells(const int32_t *coords, int64_t n, const link_grid_t *grid, uint32_t *cell_counts, void *scratch,

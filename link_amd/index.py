@@ -382,12 +382,21 @@ def strided_out_coords(coords: torch.Tensor, bounds, kernel, stride, tensor_stri
     -- else None: on the candidate rule only a superset of the box is known (kernel < stride leaves lattice points between
     the inputs' minimum and the first site), and a cached box's lower corner is what the NEXT candidate-rule layer filters
     with, so none is handed out).  Raises GridTooLarge beyond the dense-grid limit and beyond 2^31 candidate rows: the
-    callers' torch / hash-chain path takes such frames."""
+    callers' torch / hash-chain path takes such frames.  Raises ValueError for a frame whose sites or taps leave the int32 range."""
     n, dev = coords.shape[0], coords.device
     ss = [int(stride[k]) * int(tensor_stride[k]) for k in range(3)]
     (lo, hi) = bounds
     if n == 0:
         return coords.new_empty((0, 4)), None
+    # int32 rows: a site or a tap that leaves the int32 range cannot be written down (the kernels would wrap it into a wrong row),
+    # so such a frame is refused here, before any launch
+    if all(int(stride[k]) in (1, int(kernel[k])) for k in range(3)):
+        if any((lo[k] // ss[k]) * ss[k] < -2 ** 31 for k in range(3)):
+            raise ValueError(f"strided_out_coords: coordinates from {tuple(lo[:3])} floored to multiples of {tuple(ss)} leave the int32 range")
+    elif any(hi[k] + (int(kernel[k]) // 2) * int(tensor_stride[k]) > 2 ** 31 - 1 or
+             lo[k] + (1 - (int(kernel[k]) + 1) // 2) * int(tensor_stride[k]) <= -2 ** 31 for k in range(3)):
+        raise ValueError(f"strided_out_coords: kernel {tuple(kernel)} at tensor stride {tuple(tensor_stride)} over coordinates "
+                         f"{tuple(lo[:3])} .. {tuple(hi[:3])} has taps outside the int32 range")
     if all(int(stride[k]) in (1, int(kernel[k])) for k in range(3)):
         glo = [lo[k] // ss[k] for k in range(3)]
         ghi = [hi[k] // ss[k] for k in range(3)]

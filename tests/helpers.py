@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (fixture loading, seeded generators, error metrics)."""
+import contextlib
 import glob
 import json
 import os
@@ -107,3 +108,31 @@ def array_digest(a):
     a = np.asarray(a)
     a = a.astype(np.int64 if np.issubdtype(a.dtype, np.integer) else np.float32)
     return {"shape": list(a.shape), "dtype": str(a.dtype), "sha256": hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()}
+
+
+class _Spy:
+    def __init__(self, real, calls):
+        self._real, self._calls = real, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        if not name.startswith("link_"):
+            return fn
+
+        def call(*a):
+            self._calls.append(name)
+            return fn(*a)
+        return call
+
+
+@contextlib.contextmanager
+def spied():
+    """the names of the library entry points called inside the block"""
+    from link_amd import _lib as L
+    real, calls = L.lib, []
+    spy = _Spy(real(), calls)
+    L.lib = lambda: spy
+    try:
+        yield calls
+    finally:
+        L.lib = real

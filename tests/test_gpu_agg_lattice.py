@@ -59,6 +59,7 @@ import torch
 
 import agg64 as A
 import agg_frames as AF
+from helpers import spied
 from ref64 import record_row
 
 pytestmark = pytest.mark.gpu
@@ -129,34 +130,6 @@ def poison():
     for k in (10, 14, 18, 22):
         t = torch.full((1 << k,), float("nan"), device=DEV)
         del t
-
-
-class _Spy:
-    def __init__(self, real, calls):
-        self._real, self._calls = real, calls
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if not name.startswith("link_"):
-            return fn
-
-        def call(*a):
-            self._calls.append(name)
-            return fn(*a)
-        return call
-
-
-@contextlib.contextmanager
-def spied():
-    """the names of the library entry points called inside the block"""
-    from link_amd import _lib as L
-    real, calls = L.lib, []
-    spy = _Spy(real(), calls)
-    L.lib = lambda: spy
-    try:
-        yield calls
-    finally:
-        L.lib = real
 
 
 @contextlib.contextmanager
