@@ -1766,6 +1766,79 @@ int link_deform_conv_backward_weight(const link_deform_conv_geom_t *geom, const 
                                      const float *output /* nullable without LINK_DCN_RELU */, const float *grad_out,
                                      float *grad_weight, void *workspace, size_t workspace_bytes, void *stream);
 
+/* =============================================================================================
+ * Section S: the PointPillars reader and its BEV scatter (csrc/pillar.hip)
+ * Reference: detection/det3d/models/readers/pillar_encoder.py.
+ *
+ * voxels [P, T, D] fp32 are the padded pillars (x, y, z first), num_points int32 [P], coors int32 [P, 4] = b, z, y, x.  A pillar's
+ * row t < num = clamp(num_points[p], 0, T) is decorated to K1 = D + 5 (+ 1) values: the D raw ones, xyz minus the pillar's mean,
+ * x - (coors[p][3] vx + x_offset), y - (coors[p][2] vy + y_offset) and, with_distance, |xyz|; x_offset = vx / 2 + x_min as the
+ * reference's constructor forms it.  Each PFN layer is a bias-free linear map, BatchNorm in eval mode as a per-channel affine
+ * (scale = gamma / sqrt(var + eps), shift = beta - mean scale, formed inside the kernel from the module's own five tensors -- no
+ * folded copy of the parameters exists anywhere) applied AFTER the dot product, ReLU and a max over ALL T rows.  A
+ * layer that is not the last has width / 2 units and hands [x, x_max repeated] to the next one.
+ *
+ * Mean contract: the mean is the sum over rows t < num divided by num.  The reference sums all T rows; the two agree because
+ * padded input rows are zero, as every voxel generator of this library and of the reference writes them.  Rows t >= num are
+ * never read.  (The sum is formed as row 0 plus the summed offsets from row 0 over num: the same number, fewer lost bits.)
+ * Padded rows: the reference masks them to zero and still runs them through the layers, so they leave layer 1 as relu(shift1) and
+ * take part in the max.  All padded rows of a pillar are equal in both layers; one representative is evaluated where num < T.
+ * num == 0 (the reference divides 0 by 0 there and returns NaN) gives the value of an all-padded pillar: no NaN.
+ * count (nullable): a device int32; pillars p >= min(max(*count, 0), P) are inert: nothing of them is read but nothing is computed
+ * or written (link_pillar_gather and link_pillar_decorate write zeros for them).  voxel_offsets + B of link_voxelize is one.
+ * A pillar whose (b, y, x) lies outside (batch, ny, nx) writes nothing to a canvas and gathers zero.  Duplicate (b, y, x) among
+ * the live pillars make the canvas depend on the order of the writes (as in the reference); the voxelisers produce none.
+ *
+ * io_dtype is the type of rows and canvas: LINK_IO_F32 / F16 / BF16.  The reader computes in fp32 and rounds once at the store.
+ * The canvas entries zero-fill the canvas themselves (hipMemsetAsync on the stream) and use no atomics: every result is
+ * reproducible bit for bit, and the reader's canvas form equals link_pillar_scatter of its row form bit for bit.
+ * Every entry launches on the caller's stream, allocates nothing, reads nothing back and keeps no state (graph capture is fine).
+ *
+ * Native range of the reader (link_pillar_native; LINK_ERR_ARG outside it): 1 or 2 layers, every width a multiple of 16 up to
+ * LINK_PILLAR_MAX_WIDTH, 3 <= D <= LINK_PILLAR_MAX_D, 1 <= T <= LINK_PILLAR_MAX_T.  struct_bytes = sizeof(link_pillar_geom_t)
+ * (checked by every entry: the layout has no id in link_abi_struct_size).  Every entry: n_pillars <= 2^31, the canvas at most 2^40
+ * elements with ny nx <= 2^31; scatter, gather and decorate also n_pillars channels (n_pillars t) <= 2^38.  LINK_ERR_ARG otherwise,
+ * before anything is launched.
+ *
+ * link_pillar_reader    replaces PillarFeatureNet.forward (pillar_encoder.py:116-162) with PFNLayer.forward (:40-55) and, with
+ *                       `canvas`, PointPillarsScatter.forward (:182-218) as well.  Exactly one of rows [P, C] / canvas
+ *                       [batch, C, ny, nx] is non-null, C = width[layers - 1].  layer1.weight [U1, K1], layer2.weight
+ *                       [width[1], 2 U1] row-major, U1 = width[0] / 2 with two layers, width[0] with one; gamma, beta,
+ *                       running_mean, running_var one fp32 per unit.  layer2 may be null with one layer.
+ * link_pillar_scatter   replaces PointPillarsScatter.forward (:182-218): zero-fill, then rows [P, channels] -> canvas
+ * link_pillar_gather    its adjoint (what autograd derives from `canvas[:, indices] = voxels`, :208): rows <- grad_canvas
+ * link_pillar_decorate  replaces the decoration and the mask of PillarFeatureNet.forward (:129-156) for the training path:
+ *                       decorated [P, T, K1] fp32, rows t >= num and inert pillars zero.  Uses t, d, with_distance, vx .. y_offset.
+ * ============================================================================================= */
+#define LINK_PILLAR_MAX_T 64
+#define LINK_PILLAR_MAX_D 8
+#define LINK_PILLAR_MAX_WIDTH 128
+typedef struct {
+  int32_t struct_bytes;      /* sizeof(link_pillar_geom_t) */
+  int32_t t, d;              /* rows per pillar, raw values per row */
+  int32_t with_distance;
+  int32_t layers;            /* 1 or 2 */
+  int32_t width[2];          /* num_filters as configured */
+  int32_t batch, ny, nx;     /* the canvas */
+  int32_t io_dtype;          /* LINK_IO_*: rows and canvas */
+  float vx, vy, x_offset, y_offset;
+} link_pillar_geom_t;
+typedef struct {
+  const float *weight, *gamma, *beta, *running_mean, *running_var;   /* Linear.weight and the BatchNorm1d's tensors, on the device */
+  float eps;
+  int32_t reserved;
+} link_pillar_layer_t;
+int link_pillar_native(const link_pillar_geom_t *geom);   /* 1 inside the reader's native range, 0 outside */
+int link_pillar_reader(const link_pillar_geom_t *geom, const float *voxels, const int32_t *num_points, const int32_t *coors,
+                       int64_t n_pillars, const int32_t *count /* nullable */, const link_pillar_layer_t *layer1,
+                       const link_pillar_layer_t *layer2 /* nullable with one layer */, void *rows, void *canvas, void *stream);
+int link_pillar_scatter(const link_pillar_geom_t *geom, const void *rows, const int32_t *coors, int64_t n_pillars, int32_t channels,
+                        const int32_t *count /* nullable */, void *canvas, void *stream);
+int link_pillar_gather(const link_pillar_geom_t *geom, const void *grad_canvas, const int32_t *coors, int64_t n_pillars,
+                       int32_t channels, const int32_t *count /* nullable */, void *grad_rows, void *stream);
+int link_pillar_decorate(const link_pillar_geom_t *geom, const float *voxels, const int32_t *num_points, const int32_t *coors,
+                         int64_t n_pillars, const int32_t *count /* nullable */, float *decorated, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .aggregate import (aux_to_voxel, large_to_small, link_index_of, small_to_la
                         voxel_to_aux)
 from .elk import (Conv3d, ELKBlock, ElkCoreBatch, ElkCorePlan, SparseConvTensor, TSELKBlock, elk_core_autograd, elk_core_fused,
                   invalidate_derived_weights, spconv2ts, ts2spconv)
-from . import boxnms, centerloss, dcn, detaug, dethead, dettta, roihead, segio, segloss, tracker, voxelize
+from . import boxnms, centerloss, dcn, detaug, dethead, dettta, pillar, roihead, segio, segloss, tracker, voxelize
 from .boxnms import (boxes_iou3d_gpu, boxes_iou_bev, boxes_overlap_bev, circle_nms, install_as_iou3d_nms, nms_gpu, nms_normal_gpu,
                      nms_padded, rotate_nms_pcdet, to_pcdet)
 from .centerloss import CenterHeadLoss, CenterTargetAssigner, FastFocalLoss, RegLoss
@@ -28,6 +28,8 @@ from .modules import BatchNorm, LeakyReLU, ReLU, fapply, fuse_for_inference
 from .segio import SegEvaluator, SegVoxelizer, sparse_collate, sparse_collate_fn, sparse_quantize
 from .segloss import SegCriterion, lovasz_softmax, lovasz_softmax_flat
 from .roihead import BEVFeatureExtractor, ProposalTargetLayer, RoIHead, TwoStageRefiner, roi_box_points, roi_loss, roi_refine
+from .pillar import (PFNLayer, PillarFeatureNet, PillarReader, PointPillarsScatter, pillar_bev, pillar_config_native, pillar_decorate,
+                     pillar_native, pillar_scatter)
 from .pointvoxel import initial_voxelize, point_to_voxel, voxel_to_point
 from .tensor import PointTensor, SparseTensor, cat
 from .tracker import CenterTracker, boxes_to_global

@@ -187,6 +187,20 @@ class LinkDeformConvGeom(Structure):
                                        "groups", "deformable_groups", "offset_channels", "io_dtype", "flags")]
 
 
+PILLAR_MAX_T, PILLAR_MAX_D, PILLAR_MAX_WIDTH = 64, 8, 128      # section S: the reader's native range
+
+
+class LinkPillarGeom(Structure):
+    """link_pillar_geom_t (section S: the PointPillars reader); struct_bytes carries its own size, the entries check it"""
+    _fields_ = [(k, c_int32) for k in ("struct_bytes", "t", "d", "with_distance", "layers")] + [("width", c_int32 * 2)] + \
+               [(k, c_int32) for k in ("batch", "ny", "nx", "io_dtype")] + [(k, c_float) for k in ("vx", "vy", "x_offset", "y_offset")]
+
+
+class LinkPillarLayer(Structure):
+    """link_pillar_layer_t (section S: one PFN layer's Linear.weight and BatchNorm1d tensors)"""
+    _fields_ = [(k, c_void_p) for k in ("weight", "gamma", "beta", "running_mean", "running_var")] + [("eps", c_float), ("reserved", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/link_amd.h declares
 SIGNATURES = {
     "link_abi_version": (c_int, []),
@@ -423,6 +437,13 @@ SIGNATURES = {
     "link_deform_conv_forward": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 5),
     "link_deform_conv_backward_data": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 8),
     "link_deform_conv_backward_weight": (c_int, [POINTER(LinkDeformConvGeom)] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    # section S: the PointPillars reader and its BEV scatter (csrc/pillar.hip)
+    "link_pillar_native": (c_int, [POINTER(LinkPillarGeom)]),
+    "link_pillar_reader": (c_int, [POINTER(LinkPillarGeom)] + [c_void_p] * 3 + [c_int64, c_void_p, POINTER(LinkPillarLayer),
+                                   POINTER(LinkPillarLayer)] + [c_void_p] * 3),
+    "link_pillar_scatter": (c_int, [POINTER(LinkPillarGeom), c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "link_pillar_gather": (c_int, [POINTER(LinkPillarGeom), c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "link_pillar_decorate": (c_int, [POINTER(LinkPillarGeom), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
